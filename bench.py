@@ -3,6 +3,17 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W]
                     [--config c2|c2m|c2r|c3|c3p|c3r|c3s|c4|c5|c6|c6e] [--streams S] [--record 16|8]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline
+fields (`value`, `ms_per_step`, the configuration timed).  `--full` goes on
+to everything else described below — `roofline`, `variants`, `cpu_baseline`,
+the host-inclusive path, config 5's histogram check and the default line's
+sub-lines — each in runs of its own after the timed region.
+`--dump-outputs DIR` writes what the last timed step computed (records, or
+the flow histogram and ids, the rewritten frames, the emitted packets) to
+DIR/<name>.npy; the inputs are pure in (seed, index), so two builds run with
+the same arguments can be compared output for output.
 
 A *step* is one launch of the parse path over one batch of synthetic frames
 already resident in HBM.  At N=1 the default workload is BASELINE.json
@@ -1307,7 +1318,9 @@ def jsonable(x, path="line"):
 T_START = time.perf_counter()
 
 
-def main():
+def parse_args(argv=None):
+    """The command line (sys.argv by default), with what a run without --full
+    leaves out switched off."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000)
@@ -1367,12 +1380,32 @@ def main():
                          "NCCL_HOSTID and the ranks talk over loopback sockets (P2P, SHM, "
                          "InfiniBand off), so RCCL accepts them on one device; the N > 1 path "
                          "runs with real RCCL kernels, the rates mean nothing")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything else the line can "
+                         "carry: the CPU baselines, the ungated region, the roofline pass and "
+                         "PMC traffic, the variants, the host-inclusive path, config 5's "
+                         "histogram check and, for c2, the sub-lines (the --no-* options pick "
+                         "among them).  Without it the run sets up, warms up, times the steps "
+                         "and prints the headline fields only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to "
+                         "DIR/<name>.npy (float64; a fixed, seeded sample of the rows of an "
+                         "output above DUMP_BUDGET_BYTES, with <name>_rows.npy naming them; "
+                         "c6e's emitted bytes go out in 64-B rows, without the up to 63 "
+                         "bytes past the last whole row)")
+    args = ap.parse_args(argv)
+    if not args.full:
+        args.no_cpu_baseline = args.no_sublines = args.no_host_path = True
     if args.streams <= 0:
         args.streams = STREAMS.get(args.config, 2)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
     subline_names(args)  # a bad --sublines fails before any GPU work
+    return args
+
+
+def main():
+    args = parse_args()
     global CPU_WORKERS
     CPU_WORKERS = args.cpu_workers
 
@@ -1489,7 +1522,9 @@ def main():
         result["sublines"] = subs
         result["wall_s_command"] = round(time.perf_counter() - T_START, 2)
     if rank == 0:
-        print(json.dumps(jsonable(compact_line(result, args.config))), flush=True)
+        # a plain run's line is short as it is (run_config: lean_line)
+        line = compact_line(result, args.config) if args.full else result
+        print(json.dumps(jsonable(line)), flush=True)
     teardown(dist, world, getattr(ctx, "_flow_comm", None))
 
 
@@ -1745,6 +1780,7 @@ def run_sublines(args, env, run, release=lambda: None, out=None):
         sub.config, sub.streams, sub.record, sub.timing = name, STREAMS[name], 16, "launches"
         sub.no_variants, sub.no_host_path = True, True
         sub.stagger_us = None
+        sub.dump_outputs = None  # --dump-outputs writes the main line's outputs only
         sub.warmup = max(args.warmup, SUBLINE_WARMUP)
         t0 = time.perf_counter()
         line = run(sub, name, env)
@@ -1753,6 +1789,76 @@ def run_sublines(args, env, run, release=lambda: None, out=None):
         out[name] = line
         release()
     return out if env[6] == 0 else None
+
+
+# --dump-outputs: bytes of .npy a run may write, all outputs together
+# (float64: 8 B per 4 output bytes, so 8 MiB of records go out whole)
+DUMP_BUDGET_BYTES = 48 << 20
+DUMP_SEED = 20250808
+
+
+def dump_outputs(torch, out_dir, found):
+    """--dump-outputs: write each output of the last timed step as
+    out_dir/<name>.npy, float64 [rows, 32-bit little-endian words per row]
+    (every u32 is exact in a float64).  `found` = {name: (flat uint8 device
+    tensor, bytes per row)}; bytes past the last whole row are left out.  An
+    output above its share of DUMP_BUDGET_BYTES goes out as a fixed sample of
+    its rows, one drawn from each of equal strata by DUMP_SEED (the same rows
+    in every run of the same arguments), named by <name>_rows.npy."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(found))
+    for name, (buf, row_bytes) in found.items():
+        buf = buf.contiguous().view(-1).view(torch.uint8)
+        words = row_bytes // 4
+        rows = buf.numel() // (4 * words)
+        x = buf[:rows * 4 * words].view(rows, 4 * words)
+        keep = max(1, share // (8 * words + 8))
+        if rows > keep:
+            width = rows // keep
+            idx = np.arange(keep, dtype=np.int64) * width + \
+                np.random.default_rng(DUMP_SEED).integers(0, width, keep)
+            x = x[torch.from_numpy(idx).to(buf.device)]
+            np.save(out_dir / f"{name}_rows.npy", idx.astype(np.float64))
+        a = np.ascontiguousarray(x.cpu().numpy()).view("<u4").astype(np.float64)
+        np.save(out_dir / f"{name}.npy", a)
+        log(f"[bench] wrote {out_dir / name}.npy: {a.shape[0]} of {rows} rows x {words} words")
+
+
+def lean_line(args, config, world, value, ms_step, n, n_total, streams_n, reps, record_bufs,
+              gate_note, use_ring, wall, distributed):
+    """The line of a plain run (no --full): the headline fields and the
+    configuration that was timed, nothing that takes a run of its own."""
+    emit = MODES.get(config) == "emit"
+    _, _, _, chain_name, desc = CONFIGS[config]
+    return {
+        "metric": EMIT_METRIC if emit else METRIC,
+        "value": round(value, 2),
+        "unit": "Mpkt/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_step, 5),
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic (device-generated, seed 20250808)",
+        "config": {
+            "workload": desc,
+            "frames_per_gpu": n,
+            "frames_total": n_total,
+            "chain": chain_name,
+            "record_bytes": args.record,
+            "streams": streams_n,
+            "arena_copies_rotated": reps,
+            "record_buffers_rotated": record_bufs,
+            "timing": gate_note,
+            "timing_mode": "ring" if use_ring else "launches",
+        },
+        "distributed": distributed,
+        "wall_s_timed_region": round(wall, 4),
+        "full": "--full adds the CPU baselines, roofline, variants, host path and sub-lines",
+    }
 
 
 def run_config(args, config, env):
@@ -1920,6 +2026,32 @@ def run_config(args, config, env):
     frames_all = n_total
     value = frames_all * args.steps / t_sec / 1e6
     ms_step = t_sec * 1e3 / args.steps
+    if args.dump_outputs and rank == 0:
+        # what step K - 1 left behind, before anything below runs over the
+        # same buffers: (flat bytes, bytes per row) per output
+        last = args.steps - 1
+        if flows:
+            found = {"flow_hist": (hist_last, 4), "flow_ids": (fid_last, 4)}
+        elif mode == "modify":  # the frames rewritten in place
+            frames = arenas[last % reps]  # (slot rings: without the arena's slack)
+            found = {"frames": (frames[:n * stride] if stride else frames, stride or 64)}
+        elif emit:  # the packed destination arena, without its slack
+            dst = main_run.dst[last % len(main_run.dst)]
+            found = {"emitted": (dst[:dst.numel() - 64], 64)}
+        else:
+            bufs = (ring_outs if args.record == 16 else outs8) if use_ring else outs
+            found = {"records": (bufs[last % len(bufs)].view(-1)[:n * args.record], args.record)}
+        dump_outputs(torch, Path(args.dump_outputs), found)
+    line = None
+    if rank == 0:
+        line = lean_line(args, config, world, value, ms_step, n, n_total, streams_n, reps,
+                         G if use_ring else reps, gate_note, use_ring, wall,
+                         {**idist.world_info(),
+                          "region_ms_per_rank": [round(x, 5) for x in region_ms_per_rank]})
+    if not args.full:
+        if read_lazy:
+            ctx.set_tuning(_abi.TUNE_READ_PLAN, 0)
+        return line
     ungated = None
     if gate is not None:  # the same region timed from host submission, for reference
         ms_u, _ = main_run.run(args.steps)
@@ -2152,24 +2284,9 @@ def run_config(args, config, env):
                       "table-free Toeplitz hash, bit by bit from the key windows FlowArgs::w in "
                       "SGPRs; the step adds k_flow_count16 / k_flow_reduce16)"}.get(mode, "")
     read_frac_step = step_rd / (ms_step / 1e3) / 1e9 / HBM_PEAK_GBS
-    return {
-        "metric": EMIT_METRIC if emit else METRIC,
-        "value": round(value, 2),
-        "unit": "Mpkt/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_step, 5),
-        "higher_is_better": True,
-        "scaling": args.scaling,
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic (device-generated, seed 20250808)",
-        "config": {
-            "workload": desc,
-            "frames_per_gpu": n,
-            "frames_total": n_total,
-            "chain": chain_name,
+    # the plain run's line, and on top of it what --full measured
+    del line["full"]
+    line["config"].update({
             "layout": (("chunk lists: u32 pkt_seg bounds, u64 seg_off + u16 seg_len per chunk" +
                         ("; chunk 0 as one u64 (offset << 16) | length per packet"
                          if read_first else "") +
@@ -2178,19 +2295,14 @@ def run_config(args, config, env):
                         f" ({READ_CHUNKS[config]})")
                        if mode == "read" else
                        f"strided {stride} B" if stride else "packed, u64 offsets + u16 lengths"),
-            "record_bytes": args.record,
-            "streams": streams_n,
-            "arena_copies_rotated": reps,
-            "record_buffers_rotated": (G if use_ring else reps),
             "parallelism": (f"{args.scaling} scaling, contiguous share per GPU x{world}" +
                             (f"; {'gloo' if args.dist_backend == 'gloo' and world > 1 else 'RCCL'}"
                              f" all-reduce (sum) of the {FLOW_BINS} x u32 flow "
                              "histogram every step" if flows else
                              " (no data-path collective)")),
             "ok_fraction": round(ok_frac, 6),
-            "timing": gate_note,
-            "timing_mode": "ring" if use_ring else "launches",
-        },
+    })
+    line.update({
         "roofline": {
             "bound": "hbm",
             "achieved": round(achieved, 1),
@@ -2248,7 +2360,8 @@ def run_config(args, config, env):
         "cpu_baseline": cpu,
         "wall_s_timed_region": round(wall, 4),
         "host_inclusive": host_path,
-    }
+    })
+    return line
 
 
 if __name__ == "__main__":

@@ -574,6 +574,69 @@ def test_emit_config_stack_and_values():
     assert (p0 >= 0xC000).all() and (v0 < (1 << 24)).all()
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: an output within the budget goes out whole as float64
+    rows of little-endian u32 words (exact); one above it as the same seeded
+    sample of rows in every run, named by <name>_rows.npy; the files stay
+    within DUMP_BUDGET_BYTES."""
+    import torch
+
+    g = torch.Generator().manual_seed(7)
+    recs = torch.randint(0, 256, (1000, 16), dtype=torch.uint8, generator=g)
+    ids = torch.arange(5000, dtype=torch.int32) * 3
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 2 * 40 * 1000)
+    for d in ("a", "b"):
+        bench.dump_outputs(torch, tmp_path / d, {"records": (recs.view(-1), 16),
+                                                 "flow_ids": (ids, 4)})
+    a = np.load(tmp_path / "a" / "records.npy")
+    assert a.dtype == np.float64 and a.shape == (1000, 4)
+    assert (a.astype("<u4").view(np.uint8).reshape(-1, 16) == recs.numpy()).all()
+    assert not (tmp_path / "a" / "records_rows.npy").exists()
+    f, rows = np.load(tmp_path / "a" / "flow_ids.npy"), np.load(tmp_path / "a" / "flow_ids_rows.npy")
+    assert f.shape == (len(rows), 1) and 0 < len(rows) < 5000 and (np.diff(rows) > 0).all()
+    assert (f[:, 0] == 3 * rows).all()
+    total = sum(p.stat().st_size for p in (tmp_path / "a").iterdir())
+    assert total <= bench.DUMP_BUDGET_BYTES + 4 * 128  # + the .npy headers
+    for name in ("records.npy", "flow_ids.npy", "flow_ids_rows.npy"):
+        assert (tmp_path / "a" / name).read_bytes() == (tmp_path / "b" / name).read_bytes()
+
+
+def test_plain_line_keeps_the_headline_fields():
+    """A run without --full prints lean_line: the headline fields with the
+    meaning they have in the full line, and nothing measured in a run of its
+    own (no roofline, variants, CPU baseline, host path, sub-lines)."""
+    import argparse
+
+    args = argparse.Namespace(steps=20, warmup=5, scaling="weak", record=16)
+    line = bench.lean_line(args, "c2", 1, 87163.064, 0.012031, 1 << 20, 1 << 20, 2, 8, 8,
+                           "gated", False, 0.01, {"world_size": 1})
+    assert line["metric"] == bench.METRIC and line["unit"] == "Mpkt/s" and line["dtype"] == "u8"
+    assert line["value"] == 87163.06 and line["ms_per_step"] == 0.01203
+    assert line["higher_is_better"] is True and (line["steps"], line["warmup"]) == (20, 5)
+    assert not {"roofline", "variants", "cpu_baseline", "host_inclusive", "sublines"} & set(line)
+    assert bench.lean_line(args, "c6e", 1, 1.0, 1.0, 8, 8, 1, 1, 1, "", False, 0.0,
+                           {})["metric"] == bench.EMIT_METRIC
+
+
+def test_a_run_without_full_leaves_out_what_moved():
+    """bench.parse_args: without --full the CPU baselines, the sub-lines and
+    the host path are off whatever else is asked (run_config returns the lean
+    line right after the timed region: tests/test_bench_dump.py, on the GPU);
+    with --full they are on unless their own --no-* option says otherwise."""
+    plain = bench.parse_args([])
+    assert not plain.full and plain.dump_outputs is None
+    assert plain.no_cpu_baseline and plain.no_sublines and plain.no_host_path
+    assert bench.subline_names(plain) == []
+    assert (plain.gpus, plain.steps, plain.warmup, plain.config) == (1, 2000, 100, "c2")
+    full = bench.parse_args(["--full", "--steps", "20", "--warmup", "5"])
+    assert full.full and (full.steps, full.warmup) == (20, 5)
+    assert not (full.no_cpu_baseline or full.no_sublines or full.no_host_path
+                or full.no_variants)
+    assert bench.subline_names(full) == ["c3", "c4", "c5"]
+    picked = bench.parse_args(["--full", "--no-sublines", "--dump-outputs", "d"])
+    assert picked.no_sublines and not picked.no_cpu_baseline and picked.dump_outputs == "d"
+
+
 def test_teardown_is_bounded_at_n_above_one():
     """bench.teardown at N > 1: a communicator destroy that never returns
     (seen once in the one-GPU RCCL rehearsal) ends the process with exit

@@ -7,9 +7,9 @@ driver's command (`bench.py --gpus 1 --steps 20 --warmup 5`):
     python tools/region_trace.py D/run_kernel_trace.csv --warmup 5 --steps 20
 
 bench.py's parse-kernel dispatches in order: W warm-up steps, the K timed
-steps (the region), then the ungated re-run, the algorithmic-bytes parse, the
-single-stream roofline pass and the variants.  For the region's K dispatches
-this reports, on the device clock of the trace:
+steps (the region), then, under --full, the ungated re-run, the
+algorithmic-bytes parse, the single-stream roofline pass and the variants.
+For the region's K dispatches this reports, on the device clock of the trace:
   * region: first start -> last end;
   * stagger: first dispatch start -> the other stream's first start, during
     which one stream runs alone;
