@@ -495,9 +495,10 @@ int ingot_gpu_stream_delay(ingot_gpu_ctx* ctx, uint32_t ns, void* stream);
  *                              64-packet tile per wave)
  *   INGOT_TUNE_PIPELINE        strided rings (slots >= 64 B) without a length
  *                              array, 16- or 8-B records: the multi-tile kernel
- *                              that stages the next tile while parsing one
- *                              (double-buffered LDS).  0 = on, 2 blocks per CU
- *                              (default); 1 = off; k >= 2 = k tiles per wave
+ *                              (several tiles per wave, staged by LDS-DMA;
+ *                              INGOT_TUNE_PIPE_DEPTH).  0 = on, 2 blocks per CU
+ *                              or INGOT_TUNE_RING_GRID's (default); 1 = off;
+ *                              k >= 2 = k tiles per wave
  *   INGOT_TUNE_CACHE_POLICY    0 = measured default (non-temporal record
  *                              stores; the ring kernel: non-temporal staging
  *                              loads and, for 16-B records, device-scope
@@ -509,9 +510,18 @@ int ingot_gpu_stream_delay(ingot_gpu_ctx* ctx, uint32_t ns, void* stream);
  *                              2 sc1 nt, 3 sc0 sc1, 4 sc0 sc1 nt, 5 sc0;
  *                              bits 6-8, when non-zero, the staging loads'
  *                              instead of bit 0 (same codes, 6 sc0 nt)
- *   INGOT_TUNE_PIPE_DEPTH      the multi-tile ring kernel's tiles in flight
- *                              per wave (LDS images): 2 (default), 3 or 4
- *                              (the rewrite ring kernel: 2 or 3)
+ *   INGOT_TUNE_PIPE_DEPTH      the multi-tile ring kernel's LDS images per
+ *                              wave: 0 (default) = a single image, restaged
+ *                              once the walk has read it (16.4 KiB of LDS per
+ *                              block; the faster one when launches overlap on
+ *                              two streams); 2, 3 or 4 = that many tiles in
+ *                              flight, the next ones staged while one is
+ *                              parsed (2: 32.9 KiB per block; the faster one
+ *                              for launches on a single stream).  The rewrite
+ *                              ring kernel takes 2 (its default) or 3 and
+ *                              ingot_gpu_parse_ring 2 (default) to 4; 4
+ *                              means 2 for the rewrite.  Any other value,
+ *                              1 included: EINVAL
  *   INGOT_TUNE_WRITEBACK       ingot_gpu_parse_modify on slot rings: bytes
  *                              written back per edited unit, 16, 32 or 64
  *                              (0 = measured default)
@@ -548,10 +558,11 @@ int ingot_gpu_stream_delay(ingot_gpu_ctx* ctx, uint32_t ns, void* stream);
  *                              no LDS table); everything else runs k_parse's
  *                              flows mode (LDS table: 16-bit entries one tile
  *                              per wave, 32-bit entries on a persistent grid)
- *   INGOT_TUNE_RING_GRID       ingot_gpu_parse_ring: 256-thread blocks per
- *                              CU (1..8; 0 = measured default).  The ring's
- *                              tiles in flight per wave follow
- *                              INGOT_TUNE_PIPE_DEPTH
+ *   INGOT_TUNE_RING_GRID       ingot_gpu_parse_ring and the multi-tile ring
+ *                              kernel (when INGOT_TUNE_PIPELINE is 0):
+ *                              256-thread blocks per CU (1..8; 0 = measured
+ *                              default, 2).  The tiles in flight per wave
+ *                              follow INGOT_TUNE_PIPE_DEPTH
  *   INGOT_TUNE_XCD_REMAP       slot-ring kernels (parse, rewrite) tile order:
  *                              0 = measured default (= 1); 1 = blocks
  *                              renumbered XCD-major (block b runs on XCD b % 8;

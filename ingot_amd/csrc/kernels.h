@@ -173,7 +173,8 @@ struct Tuning {
     int window_strided = 0;
     uint32_t max_blocks = 0;
     int pipeline = 0;  // ring kernel: 0 = auto (2 blocks per CU), 1 = off, k = k tiles per wave
-    int pipe_depth = 0;    // ring kernel: tiles in flight per wave (0 = 2)
+    int pipe_depth = 0;    // ring kernels: LDS images per wave, 2..4; 0 = the default: one image
+                           // restaged in place (slot-ring parse), 2 (consumer, rewrite)
     int writeback = 0;     // ring rewrite kernel: write-back unit (0 = measured default)
     int cache_policy = 0;  // bit 0: nt staging loads; bit 1: nt record stores
     int flow_table = 0;    // flows: 0 = auto (16-bit table when it suffices), 32 = 32-bit
@@ -181,7 +182,7 @@ struct Tuning {
     int read_plan = 0;     // parse_read: 0 / 11 line-completing chunk-0 window, 1 = 4 pieces,
                            // 17 = chunk bounds loaded lazily (parse_read_first)
     int flow_kernel = 0;   // flows: 0 / 15 = the measured default (k_flows_bits when it applies)
-    int ring_grid = 0;     // ring consumer: blocks per CU (0 = measured default)
+    int ring_grid = 0;     // ring consumer and slot-ring parse: blocks per CU (0 = default, 2)
     int ring_groups = 0;   // ring consumer: batches in flight at once (0 = measured default)
     int xcd_remap = 0;     // slot ring: 1 = each XCD's blocks take a contiguous share of tiles
     uint32_t cus = 256;  // compute units of the context's device (grid shaping)

@@ -11,7 +11,8 @@ namespace {
 // Pipelined variant for fixed slots with no length array (C2-style rings):
 // each wave walks several tiles and keeps the next DEPTH-1 tiles' LDS-DMA in
 // flight while it parses the current one (DEPTH LDS images per wave, used
-// round robin).  Requires stride >= 16*NCH.
+// round robin).  DEPTH 1: a single image, restaged once the walk has read it.
+// Requires stride >= 16*NCH.
 // POL != 0: the cache-policy word fixed at compile time (the launcher's
 // defaults), so the staging loads and record stores carry their cache bits
 // directly instead of the runtime policy switch around every instruction
@@ -82,6 +83,42 @@ __global__ __launch_bounds__(BLOCK) void k_parse_pipe(ParseArgs a) {
         step = nw;
     }
     if (t >= tend) return;
+    if constexpr (DEPTH == 1) {
+        // One image per wave (16.4 KiB per block instead of 32.9): the next
+        // tile is staged into the image just parsed, between the walk and the
+        // record store, so its loads fly during the pack, the store and the
+        // loop overhead only.  Alone on the device it is the slower kernel;
+        // beside an overlapping launch on a second stream it is the faster
+        // one, at half the LDS per block.
+        stage(t, img0);
+        // the first tile's loads are the youngest vector-memory operations
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        for (;;) {
+            const uint64_t i = t * WAVE + lane;
+            Frame<NCH> fr{(const lds_u32*)img0, lane, 0u, take, a.stride, a.arena + i * a.stride};
+            Rec r;
+            walk<CHAIN, false>(fr, r, nullptr, nullptr);
+            // every lane's LDS reads of the image have returned before it is
+            // restaged (the walk of every chain reads it data-dependently, so
+            // not before the walk is over; bytes past the window come from
+            // fr.g and are unaffected) — k_modify_pipe's rule
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            const uint64_t tn = t + step;
+            const bool more = tn < tend;
+            if (more) stage(tn, img0);
+            if (i < a.n) {
+                if constexpr (MODE == OUT_REC8) store_rec(static_cast<uint2*>(a.out) + i, pack8(r), pol);
+                else store_rec(static_cast<uint4*>(a.out) + i, pack(r), pol);
+            }
+            if (!more) break;
+            t = tn;
+            // younger than the new tile's loads is only the one record store
+            // above (lane 0 of a tile below tend is always a valid slot, so
+            // the store is always issued); operations retire in issue order
+            asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+        }
+        return;
+    }
     // prologue: the first DEPTH-1 tiles
 #pragma unroll
     for (uint32_t d = 0; d + 1u < DEPTH; ++d)
@@ -453,7 +490,7 @@ constexpr uint32_t kModifyRingWb = 64;
 constexpr uint32_t kModifyRingPolicy = 3;  // nt staging loads + nt write-back
 
 // C2-style rings (slots >= 64 B, no length array, record output): the
-// double-buffered multi-tile kernel.  Its grid is a whole number of blocks
+// multi-tile kernel.  Its grid is a whole number of blocks
 // per CU (default 2), so the tiles spread evenly; measured on MI355X (1 M x
 // 64 B, interleaved A/B): 16.6-16.7 vs 18.6-18.8 us per launch on one
 // stream, 13.5-13.6 vs 14.2-14.4 us per step on two; 6 or 12 tiles per
@@ -474,11 +511,26 @@ hipError_t launch_slot_ring(const ParseArgs& args, int chain, int mode, const Tu
         const uint64_t waves = (tiles + (uint64_t)t.pipeline - 1) / (uint64_t)t.pipeline;
         blocks = (waves + WAVES - 1) / WAVES;
     } else {
-        const uint64_t cap = 2ull * t.cus;
+        // blocks per CU: INGOT_TUNE_RING_GRID (as for the ring consumer)
+        const uint64_t cap = (t.ring_grid ? (uint64_t)t.ring_grid : 2ull) * t.cus;
         blocks = (tiles + WAVES - 1) / WAVES;
         if (blocks > cap) blocks = cap;
     }
     const uint32_t pg = (uint32_t)(blocks ? blocks : 1);
+    // Default: one LDS image per wave (k_parse_pipe DEPTH 1), measured on the
+    // two-stream C2 schedule against two images, alternated runs of the
+    // benchmark's default command: 11.59-11.64 vs 11.87-11.94 us/step
+    // (profiles/r07_c2_single_image_ab.json); a launch on one
+    // stream alone is slower (14.94 vs 14.60 us), INGOT_TUNE_PIPE_DEPTH = 2
+    // brings the second image back (the key's value 1 stays EINVAL: the
+    // single image is what 0, the default, selects).
+    if (t.pipe_depth == 0) {
+        // the default policies compiled in, as below
+        if (mode == OUT_REC16 && a.policy == 11u) return launch_pipe<4, 1, OUT_REC16, 11u>(a, chain, pg, s);
+        if (mode == OUT_REC8 && a.policy == 3u) return launch_pipe<4, 1, OUT_REC8, 3u>(a, chain, pg, s);
+        return mode == OUT_REC8 ? launch_pipe<4, 1, OUT_REC8>(a, chain, pg, s)
+                                : launch_pipe<4, 1, OUT_REC16>(a, chain, pg, s);
+    }
     if (t.pipe_depth == 3)
         return mode == OUT_REC8 ? launch_pipe<4, 3, OUT_REC8>(a, chain, pg, s)
                                 : launch_pipe<4, 3, OUT_REC16>(a, chain, pg, s);

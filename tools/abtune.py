@@ -6,8 +6,8 @@ cross-process/device variance that looks like a kernel property).
     python tools/abtune.py --config c3 --var win_i=4 --var win_i=5 --var win_i=9
     python tools/abtune.py --config c2 --var streams=1 --var streams=2 --var rec=8
 
-A variant is a comma list of key=value: win_i, win_s, blocks, pipe, depth, pol,
-wb, ftab, slow, plan, fk, streams, rec, fonly (1: the flows kernel alone, no
+A variant is a comma list of key=value: win_i, win_s, blocks, pipe, depth, grid
+(blocks per CU, INGOT_TUNE_RING_GRID), pol, wb, ftab, slow, plan, fk, streams, rec, fonly (1: the flows kernel alone, no
 histogram), mode (parse|flows|modify: the runner; default the config's).
 """
 from __future__ import annotations
@@ -39,7 +39,7 @@ def main():
     from ingot_amd.abi import (TUNE_CACHE_POLICY, TUNE_MAX_BLOCKS, TUNE_PIPE_DEPTH,
                                TUNE_PIPELINE, TUNE_WINDOW_INDEXED, TUNE_WINDOW_STRIDED,
                                TUNE_WRITEBACK, TUNE_FLOW_TABLE, TUNE_SLOW_PATH,
-                               TUNE_READ_PLAN, TUNE_FLOW_KERNEL)
+                               TUNE_READ_PLAN, TUNE_FLOW_KERNEL, TUNE_RING_GRID)
 
     prof, n, stride, chain_name, _ = bench.CONFIGS[args.config]
     chain = Chain[chain_name]
@@ -75,6 +75,8 @@ def main():
             ctx.set_tuning(TUNE_PIPELINE, int(kv["pipe"]))
         if "depth" in kv:
             ctx.set_tuning(TUNE_PIPE_DEPTH, int(kv["depth"]))
+        if "grid" in kv:
+            ctx.set_tuning(TUNE_RING_GRID, int(kv["grid"]))
         if "pol" in kv:
             ctx.set_tuning(TUNE_CACHE_POLICY, int(kv["pol"]))
         if "wb" in kv:

@@ -185,6 +185,24 @@ def main():
                                      w8.view(np.uint8).reshape(n, -1)).any(axis=1).sum())}
         res[f"{chain.name}/ring64"] = r
         print(chain.name, "ring64", r, flush=True)
+        # every LDS-image count of the ring kernel (0 = the default, a single
+        # image restaged in place) at 1 to 4 blocks per CU
+        from ingot_amd.abi import TUNE_PIPE_DEPTH, TUNE_RING_GRID
+
+        for depth in (0, 2, 3, 4):
+            for grid in (1, 2, 3, 4) if depth <= 2 else (0,):
+                c5 = ingot_amd.Context(0)
+                c5.set_tuning(TUNE_PIPE_DEPTH, depth)
+                c5.set_tuning(TUNE_RING_GRID, grid)
+                d16 = c5.parse_strided(arena, 64, n, chain)
+                d8 = c5.parse_strided_compact(arena, 64, n, chain)
+                torch.cuda.synchronize()
+                key = f"{chain.name}/ring64/depth{depth}/grid{grid}"
+                res[key] = {"record_mismatches": int((~(d16 == g16).all(dim=1)).sum().item()) + bad16,
+                            "rec8_mismatches": int((~(d8 == g8).all(dim=1)).sum().item()) +
+                            r["rec8_mismatches"]}
+                print(key, res[key], flush=True)
+                del d16, d8
         del arena, g16, g8
         torch.cuda.empty_cache()
     # batched Emit (ingot_gpu_emit_packets / _headers): random header blocks

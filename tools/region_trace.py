@@ -63,7 +63,26 @@ def main():
     # batches completed per us inside the overlap, from dispatch time shares
     share = sum(max(0.0, min(x["end_us"], hi) - max(x["start_us"], lo)) / x["dur_us"] for x in d)
     steady_us = (hi - lo) / share if share > 0 else None
+    # residency: time with 0, 1 and >= 2 dispatches running, and the stretches
+    # with exactly one (a launch draining / its successor ramping beside none)
+    ev = sorted([(x["start_us"], 1) for x in d] + [(x["end_us"], -1) for x in d])
+    held, solo, live, prev = [0.0, 0.0, 0.0], [], 0, 0.0
+    for at, step in ev:
+        held[min(live, 2)] += at - prev
+        if live == 1 and at > prev:
+            if solo and solo[-1][1] == prev:
+                solo[-1][1] = at
+            else:
+                solo.append([prev, at])
+        live, prev = live + step, at
+    inner = [b - a for a, b in solo if a >= lo and b <= hi]
     out = {
+        "idle_us": round(held[0], 3),
+        "one_kernel_us": round(held[1], 3),
+        "two_kernels_us": round(held[2], 3),
+        "one_kernel_stretches_in_overlap": len(inner),
+        "one_kernel_stretch_us_median": round(statistics.median(inner), 3) if inner else None,
+        "one_kernel_us_in_overlap": round(sum(inner), 3),
         "dispatches": len(d),
         "streams": len(queues),
         "region_us": round(region, 3),
