@@ -8,6 +8,66 @@
 namespace ingot_gpu {
 namespace {
 
+// A wave-uniform 64-bit value the compiler computed in VGPRs (a 64-bit
+// division has no scalar form), moved to an SGPR pair.
+__device__ __forceinline__ uint64_t uniform64(uint64_t v) {
+    uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32));
+    // (pinned: a readfirstlane of a value known to be uniform folds away and
+    // leaves the VGPR pair)
+    asm volatile("" : "+s"(lo), "+s"(hi));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// stage16p (walk.h) with the instruction's immediate offset OFF, which the
+// hardware adds to the source address AND to the LDS destination
+// (k_parse_pipe's 64-B slots: chunk instruction k of a tile is 1 KiB further
+// in both).
+template <int OFF>
+__device__ __forceinline__ void stage16p_at(const uint8_t* src, uint32_t* dst, uint32_t pol) {
+#define INGOT_LD(bits) __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)dst, 16, OFF, bits)
+    switch ((pol >> 6) & 7u) {
+    case 1: INGOT_LD(16); return;
+    case 2: INGOT_LD(18); return;
+    case 3: INGOT_LD(17); return;
+    case 4: INGOT_LD(19); return;
+    case 5: INGOT_LD(1); return;
+    case 6: INGOT_LD(3); return;
+    default:
+        if (pol & 1u) INGOT_LD(2);
+        else INGOT_LD(0);
+    }
+#undef INGOT_LD
+}
+
+// store_rec (walk.h: the same policy bits, the same asm form and s_nop) at a
+// wave-uniform base (SGPR pair) plus a 32-bit per-lane byte offset: no 64-bit
+// address arithmetic per lane.
+#define INGOT_ST(op, bits) asm volatile(op " %0, %1, %2 " bits "\n\ts_nop 1" ::"v"(voff), "v"(x), "s"(base) : "memory")
+#define INGOT_ST_SWITCH(op)                                    \
+    switch ((pol >> 3) & 7u) {                                 \
+    case 1: INGOT_ST(op, "sc1"); return;                       \
+    case 2: INGOT_ST(op, "sc1 nt"); return;                    \
+    case 3: INGOT_ST(op, "sc0 sc1"); return;                   \
+    case 4: INGOT_ST(op, "sc0 sc1 nt"); return;                \
+    case 5: INGOT_ST(op, "sc0"); return;                       \
+    default: if (pol & 2u) { INGOT_ST(op, "nt"); return; }     \
+    }
+__device__ __forceinline__ void store_rec_at(uint8_t* base, uint32_t voff, const uint4& v,
+                                             uint32_t pol) {
+    const u32x4 x{v.x, v.y, v.z, v.w};
+    INGOT_ST_SWITCH("global_store_dwordx4")
+    st_global(reinterpret_cast<uint4*>(base + voff), v);
+}
+__device__ __forceinline__ void store_rec_at(uint8_t* base, uint32_t voff, const uint2& v,
+                                             uint32_t pol) {
+    const u32x2 x{v.x, v.y};
+    INGOT_ST_SWITCH("global_store_dwordx2")
+    st_global(reinterpret_cast<uint2*>(base + voff), v);
+}
+#undef INGOT_ST_SWITCH
+#undef INGOT_ST
+
 // Pipelined variant for fixed slots with no length array (C2-style rings):
 // each wave walks several tiles and keeps the next DEPTH-1 tiles' LDS-DMA in
 // flight while it parses the current one (DEPTH LDS images per wave, used
@@ -24,33 +84,17 @@ __global__ __launch_bounds__(BLOCK) void k_parse_pipe(ParseArgs a) {
     constexpr uint32_t WAVE_DW = WAVE * NCH * 4u;
     constexpr uint32_t IMG_DW = WAVES * WAVE_DW + 16u;
     __shared__ __attribute__((aligned(16))) uint32_t s_img[DEPTH * IMG_DW];
+    constexpr uint32_t REC_B = MODE == OUT_REC8 ? 8u : 16u;
     const uint32_t lane = threadIdx.x & (WAVE - 1u);
-    const uint32_t wave = threadIdx.x / WAVE;
+    // wave-uniform (readfirstlane, as in k_parse_ring): the tile cursor, the
+    // tile's source and record bases and the loop control stay in SGPRs, and
+    // the staging instructions' LDS destinations (M0) are loop constants
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
     uint32_t* img0 = s_img + wave * WAVE_DW;
     const uint64_t ntiles = (a.n + WAVE - 1u) / WAVE;
-    const uint32_t take = a.stride < WIN ? a.stride : WIN;
-
-    auto stage = [&](uint64_t tt, uint32_t* img) {
-#pragma unroll
-        for (uint32_t k = 0; k < NCH; ++k) {
-            const uint32_t q = k * WAVE + lane;
-            const uint32_t pp = q / NCH;
-            const uint32_t c = (q - pp * NCH) ^ swz<NCH>(pp);
-            uint64_t slot = tt * WAVE + pp;
-            if (slot >= a.n) slot = a.n - 1u;  // a valid address for the tail tile
-            stage16p(a.arena + slot * a.stride + 16u * c, img + k * WAVE * 4u, pol);
-        }
-    };
-    auto parse = [&](uint64_t tt, const uint32_t* img) {
-        const uint64_t i = tt * WAVE + lane;
-        Frame<NCH> fr{(const lds_u32*)img, lane, 0u, take, a.stride, a.arena + i * a.stride};
-        Rec r;
-        walk<CHAIN, false>(fr, r, nullptr, nullptr);
-        if (i < a.n) {
-            if constexpr (MODE == OUT_REC8) store_rec(static_cast<uint2*>(a.out) + i, pack8(r), pol);
-            else store_rec(static_cast<uint4*>(a.out) + i, pack(r), pol);
-        }
-    };
+    // only the batch's last tile can hold slots >= n (none if 64 divides n)
+    const uint64_t ttail = a.n % WAVE ? ntiles - 1u : ~0ull;
+    const uint32_t tail_last = (uint32_t)((a.n - 1u) % WAVE);  // its last valid lane
 
     // Tile order (INGOT_TUNE_XCD_REMAP).  Bit 0: block b runs on XCD b % 8;
     // renumbered (b % 8) * G/8 + b / 8 ("XCD-major"), each XCD's blocks take
@@ -82,68 +126,172 @@ __global__ __launch_bounds__(BLOCK) void k_parse_pipe(ParseArgs a) {
         tend = ntiles;
         step = nw;
     }
+    t = uniform64(t);
+    step = uniform64(step);
+    tend = uniform64(tend);
     if (t >= tend) return;
-    if constexpr (DEPTH == 1) {
-        // One image per wave (16.4 KiB per block instead of 32.9): the next
-        // tile is staged into the image just parsed, between the walk and the
-        // record store, so its loads fly during the pack, the store and the
-        // loop overhead only.  Alone on the device it is the slower kernel;
-        // beside an overlapping launch on a second stream it is the faster
-        // one, at half the LDS per block.
-        stage(t, img0);
-        // the first tile's loads are the youngest vector-memory operations
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        for (;;) {
-            const uint64_t i = t * WAVE + lane;
-            Frame<NCH> fr{(const lds_u32*)img0, lane, 0u, take, a.stride, a.arena + i * a.stride};
+    // The tile loop, once for 64-B slots (S64) and once for every other
+    // stride (a wave-uniform choice).  A tile's staging addresses are a
+    // scalar base (arena + t * 64 * stride, advanced by a constant per tile)
+    // plus a per-lane 32-bit offset that is the same in every tile: chunk
+    // instruction k covers packets 16k .. 16k+15 of the tile, lane L chunk
+    // (L % 4) ^ swz of packet 16k + L/4.  S64: swz(16k + L/4) = (L >> 4) & 3
+    // for every k, so the four instructions differ by 16 * stride = 1 KiB in
+    // the source and by 1 KiB in the image, which is the instruction's
+    // immediate offset (added to both).  Otherwise: four offsets in VGPRs.
+    auto run = [&](auto s64) {
+        constexpr bool S64 = decltype(s64)::value;
+        static_assert(!S64 || NCH == 4, "the immediate-offset form is NCH == 4's");
+        const uint32_t stride = S64 ? 64u : a.stride;
+        const uint32_t take = stride < WIN ? stride : WIN;
+        uint32_t voff[NCH];
+#pragma unroll
+        for (uint32_t k = 0; k < NCH; ++k) {
+            const uint32_t q = k * WAVE + lane;
+            const uint32_t pp = q / NCH;
+            voff[k] = pp * stride + 16u * ((q - pp * NCH) ^ swz<NCH>(pp));
+        }
+        const uint32_t frame_off = lane * stride;  // the lane's frame in its tile
+        const uint32_t rec_off = lane * REC_B;     // and its record
+        const uint64_t tile_b = (uint64_t)WAVE * stride;
+        const uint64_t dsrc = step * tile_b;  // per step of the tile cursor
+        const uint64_t dout = step * (WAVE * REC_B);
+
+        // Tile tt, its first slot at src, into img.  The empty asm keeps each
+        // offset a 32-bit VGPR at the point of use: hoisted out of the loop
+        // as a zero-extended pair, it costs a second register and the
+        // instruction loses its scalar-base form (a 64-bit add per chunk).
+        auto stage = [&](uint64_t tt, const uint8_t* src, uint32_t* img) {
+            if (tt == ttail) {
+                // slots >= n of the tail tile: a valid address (the last slot)
+                uint32_t l = lane;
+                asm volatile("" : "+v"(l));
+#pragma unroll
+                for (uint32_t k = 0; k < NCH; ++k) {
+                    const uint32_t q = k * WAVE + l;
+                    const uint32_t pp = q / NCH;
+                    const uint32_t c = (q - pp * NCH) ^ swz<NCH>(pp);
+                    const uint32_t slot = pp < tail_last ? pp : tail_last;
+                    stage16p(src + (slot * stride + 16u * c), img + k * WAVE * 4u, pol);
+                }
+            } else if constexpr (S64) {
+                uint32_t vo = voff[0];
+                asm volatile("" : "+v"(vo));
+                stage16p_at<0>(src + vo, img, pol);
+                stage16p_at<1024>(src + vo, img, pol);
+                stage16p_at<2048>(src + vo, img, pol);
+                stage16p_at<3072>(src + vo, img, pol);
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < NCH; ++k) {
+                    uint32_t vo = voff[k];
+                    asm volatile("" : "+v"(vo));
+                    stage16p(src + vo, img + k * WAVE * 4u, pol);
+                }
+            }
+        };
+        // The lane's view of tile tt staged in img.  Bytes past the window
+        // are read through fr.g; a 64-B slot has none (the window is the
+        // whole slot, and every read is bounds-checked against len = 64), so
+        // no pointer is formed for it.  A tail tile's lanes past n hold the
+        // last slot's bytes and point at it.
+        auto frame = [&](uint64_t tt, const uint8_t* src, const uint32_t* img) {
+            const uint8_t* g = nullptr;
+            if constexpr (!S64)
+                g = src + (tt == ttail && lane > tail_last ? tail_last * stride : frame_off);
+            return Frame<NCH>{(const lds_u32*)img, lane, 0u, take, stride, g};
+        };
+        // record of tile tt, whose first record is at dst
+        auto emit = [&](uint64_t tt, uint8_t* dst, const Rec& r) {
+            if (tt == ttail && lane > tail_last) return;
+            if constexpr (MODE == OUT_REC8) store_rec_at(dst, rec_off, pack8(r), pol);
+            else store_rec_at(dst, rec_off, pack(r), pol);
+        };
+
+        const uint8_t* src = a.arena + t * tile_b;  // tile t's first slot
+        uint8_t* dst = static_cast<uint8_t*>(a.out) + t * (WAVE * REC_B);  // and record
+        if constexpr (DEPTH == 1) {
+            // One image per wave (16.4 KiB per block instead of 32.9): the
+            // next tile is staged into the image just parsed, between the
+            // walk and the record store, so its loads fly during the pack,
+            // the store and the loop overhead only.  Alone on the device it
+            // is the slower kernel; beside an overlapping launch on a second
+            // stream it is the faster one, at half the LDS per block
+            // (DESIGN.md §4.2).
+            stage(t, src, img0);
+            // the first tile's loads are the youngest vector-memory operations
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            for (;;) {
+                Frame<NCH> fr = frame(t, src, img0);
+                Rec r;
+                walk<CHAIN, false>(fr, r, nullptr, nullptr);
+                // every lane's LDS reads of the image have returned before it
+                // is restaged (the walk of every chain reads it
+                // data-dependently, so not before the walk is over; bytes
+                // past the window come from fr.g and are unaffected) —
+                // k_modify_pipe's rule
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                const uint64_t tn = t + step;
+                const bool more = tn < tend;
+                if (more) stage(tn, src + dsrc, img0);
+                emit(t, dst, r);
+                if (!more) break;
+                t = tn;
+                src += dsrc;
+                dst += dout;
+                // younger than the new tile's four loads is only the one
+                // record store above (lane 0 of every tile is a valid slot,
+                // so the store is always issued); operations retire in issue
+                // order
+                asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+            }
+            return;
+        }
+        // the staging cursor runs DEPTH-1 tiles ahead of the parse cursor
+        uint64_t ts = t;
+        const uint8_t* ssrc = src;
+        // prologue: the first DEPTH-1 tiles
+#pragma unroll
+        for (uint32_t d = 0; d + 1u < DEPTH; ++d) {
+            if (ts < tend) stage(ts, ssrc, img0 + d * IMG_DW);
+            ts += step;
+            ssrc += dsrc;
+        }
+        for (uint32_t j = 0;; ++j) {
+            if (ts < tend) {
+                stage(ts, ssrc, img0 + ((j + DEPTH - 1u) % DEPTH) * IMG_DW);
+                // tile j's loads have landed (vector-memory ops retire in
+                // issue order, stores and LDS-DMA alike): younger than them
+                // are the DEPTH-1 later tiles' loads and, once the pipeline
+                // is full, the DEPTH-1 record stores of the tiles before j —
+                // which need not have completed (counting them out left every
+                // tile waiting for the previous record's write-through)
+                if (j + 1u >= DEPTH)
+                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1u) * (NCH + 1u)) : "memory");
+                else
+                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1u) * NCH) : "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            ts += step;
+            ssrc += dsrc;
+            Frame<NCH> fr = frame(t, src, img0 + (j % DEPTH) * IMG_DW);
             Rec r;
             walk<CHAIN, false>(fr, r, nullptr, nullptr);
-            // every lane's LDS reads of the image have returned before it is
-            // restaged (the walk of every chain reads it data-dependently, so
-            // not before the walk is over; bytes past the window come from
-            // fr.g and are unaffected) — k_modify_pipe's rule
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            const uint64_t tn = t + step;
-            const bool more = tn < tend;
-            if (more) stage(tn, img0);
-            if (i < a.n) {
-                if constexpr (MODE == OUT_REC8) store_rec(static_cast<uint2*>(a.out) + i, pack8(r), pol);
-                else store_rec(static_cast<uint4*>(a.out) + i, pack(r), pol);
-            }
-            if (!more) break;
-            t = tn;
-            // younger than the new tile's loads is only the one record store
-            // above (lane 0 of a tile below tend is always a valid slot, so
-            // the store is always issued); operations retire in issue order
-            asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+            emit(t, dst, r);
+            t += step;
+            if (t >= tend) break;
+            src += dsrc;
+            dst += dout;
         }
-        return;
-    }
-    // prologue: the first DEPTH-1 tiles
-#pragma unroll
-    for (uint32_t d = 0; d + 1u < DEPTH; ++d)
-        if (t + d * step < tend) stage(t + d * step, img0 + d * IMG_DW);
-    for (uint32_t j = 0;; ++j) {
-        const uint64_t tn = t + (DEPTH - 1u) * step;
-        if (tn < tend) {
-            stage(tn, img0 + ((j + DEPTH - 1u) % DEPTH) * IMG_DW);
-            // tile j's loads have landed (vector-memory ops retire in issue
-            // order, stores and LDS-DMA alike): younger than them are the
-            // DEPTH-1 later tiles' loads and, once the pipeline is full, the
-            // DEPTH-1 record stores of the tiles before j — which need not
-            // have completed (counting them out left every tile waiting for
-            // the previous record's write-through)
-            if (j + 1u >= DEPTH)
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1u) * (NCH + 1u)) : "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1u) * NCH) : "memory");
-        } else {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    };
+    if constexpr (NCH == 4) {
+        if (a.stride == 64u) {
+            run(std::true_type{});
+            return;
         }
-        parse(t, img0 + (j % DEPTH) * IMG_DW);
-        t += step;
-        if (t >= tend) break;
     }
+    run(std::false_type{});
 }
 
 // One 32-bit word read past every cache (system scope: a doorbell in pinned
@@ -523,7 +671,9 @@ hipError_t launch_slot_ring(const ParseArgs& args, int chain, int mode, const Tu
     // (profiles/r07_c2_single_image_ab.json); a launch on one
     // stream alone is slower (14.94 vs 14.60 us), INGOT_TUNE_PIPE_DEPTH = 2
     // brings the second image back (the key's value 1 stays EINVAL: the
-    // single image is what 0, the default, selects).
+    // single image is what 0, the default, selects).  With the scalar tile
+    // loop (round 8, profiles/r08_c2_lean_loop_ab.json): 11.41-11.47 against
+    // the parent's 11.61-11.68 us/step, one stream alone 14.00 against 14.9.
     if (t.pipe_depth == 0) {
         // the default policies compiled in, as below
         if (mode == OUT_REC16 && a.policy == 11u) return launch_pipe<4, 1, OUT_REC16, 11u>(a, chain, pg, s);
