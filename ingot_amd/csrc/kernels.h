@@ -1,5 +1,7 @@
 // kernels.h — internal interface between the C ABI (api.cpp) and the HIP
-// kernels (parse.hip).  Not part of the public ABI.
+// kernels: the argument blocks, the tuning record and the launchers of
+// parse.hip, read.hip, ring.hip, tuple.hip, packed.hip, flow.hip, header.hip,
+// emit.hip and stream.hip.  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -54,7 +56,7 @@ struct ParseArgs {
     // LAYOUT_SEGMENTED, optional (ingot_gpu_parse_read_first): per packet,
     // chunk 0's (offset << 16) | length, indexed like pkt_seg
     const uint64_t* first = nullptr;
-    uint32_t xcd_remap = 0;  // k_parse_pipe: logical block = XCD-major (INGOT_TUNE_XCD_REMAP)
+    uint32_t xcd_remap = 0;  // ring kernels: tile-order bits (ring.hip: xcd_bits, k_parse_pipe)
 };
 
 struct FlowArgs {
@@ -172,9 +174,11 @@ struct Tuning {
     int window_indexed = 0;
     int window_strided = 0;
     uint32_t max_blocks = 0;
-    int pipeline = 0;  // ring kernel: 0 = auto (2 blocks per CU), 1 = off, k = k tiles per wave
-    int pipe_depth = 0;    // ring kernels: LDS images per wave, 2..4; 0 = the default: one image
-                           // restaged in place (slot-ring parse), 2 (consumer, rewrite)
+    int pipeline = 0;  // ring kernels: 0 = auto (ring_grid blocks per CU), 1 = off, k = k tiles
+                       // per wave
+    int pipe_depth = 0;    // ring kernels: LDS images per wave, 2..4 (rewrite: 2 or 3); 0 = the
+                           // default: one image restaged in place (slot-ring parse), 2
+                           // (consumer, rewrite)
     int writeback = 0;     // ring rewrite kernel: write-back unit (0 = measured default)
     int cache_policy = 0;  // bit 0: nt staging loads; bit 1: nt record stores
     int flow_table = 0;    // flows: 0 = auto (16-bit table when it suffices), 32 = 32-bit
@@ -182,7 +186,8 @@ struct Tuning {
     int read_plan = 0;     // parse_read: 0 / 11 line-completing chunk-0 window, 1 = 4 pieces,
                            // 17 = chunk bounds loaded lazily (parse_read_first)
     int flow_kernel = 0;   // flows: 0 / 15 = the measured default (k_flows_bits when it applies)
-    int ring_grid = 0;     // ring consumer and slot-ring parse: blocks per CU (0 = default, 2)
+    int ring_grid = 0;     // ring consumer and slot-ring parse: blocks per CU (0 = default, 2;
+                           // the rewrite kernel's grid is always 2 per CU)
     int ring_groups = 0;   // ring consumer: batches in flight at once (0 = measured default)
     int xcd_remap = 0;     // slot ring: 1 = each XCD's blocks take a contiguous share of tiles
     uint32_t cus = 256;  // compute units of the context's device (grid shaping)

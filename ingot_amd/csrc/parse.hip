@@ -131,14 +131,11 @@ __global__ __launch_bounds__(BLOCK) void k_parse(ARGS args) {
             nch = staged > 0 ? ((uint32_t)staged + 15u) >> 4 : 0u;
         }
 
-        // Stage: instruction k, lane L fills LDS slot q = 64k + L, i.e.
-        // packet p = q / NCH, swizzled chunk c.  (LDS-DMA: lane-linear image.)
+        // Stage: instruction k, lane L fills LDS slot 64k + L, i.e. chunk c of
+        // packet pp (walk.h: chunk_of).  (LDS-DMA: lane-linear image.)
 #pragma unroll
         for (uint32_t k = 0; k < (NCH ? NCH : 1u) && NCH; ++k) {
-            const uint32_t q = k * WAVE + lane;
-            constexpr uint32_t NCH1 = NCH ? NCH : 1u;
-            const uint32_t pp = q / NCH1;
-            const uint32_t c = (q - pp * NCH1) ^ swz<NCH>(pp);
+            const auto [pp, c] = chunk_of<NCH>(k, lane);
             const uint32_t np = (uint32_t)__shfl((int)nch, (int)pp);
             int64_t bp;
             if constexpr (LAYOUT == LAYOUT_STRIDED) {
@@ -228,25 +225,11 @@ hipError_t launch_chain(const ARGS& a, int chain, uint32_t grid, hipStream_t s,
         }
         hipLaunchKernelGGL(kernel, dim3(g), dim3(BLOCK), 0, s, a);
     };
-    switch (chain) {
-    case INGOT_CHAIN_UDP_PARSER:
-        go(k_parse<NCH, LAYOUT, INGOT_CHAIN_UDP_PARSER, MODE, ARGS>);
-        break;
-    case INGOT_CHAIN_GENERIC_ULP:
-        go(k_parse<NCH, LAYOUT, INGOT_CHAIN_GENERIC_ULP, MODE, ARGS>);
-        break;
-    case INGOT_CHAIN_VLAN_ULP:
-        go(k_parse<NCH, LAYOUT, INGOT_CHAIN_VLAN_ULP, MODE, ARGS>);
-        break;
-    default:
-        if constexpr (MODE == OUT_REC8) {
-            return hipErrorInvalidValue;  // not offered for the tunnel (api.cpp)
-        } else {
-            go(k_parse<NCH, LAYOUT, INGOT_CHAIN_GENEVE_OVER_V6, MODE, ARGS>);
-        }
-        break;
-    }
-    return hipGetLastError();
+    // any other tag is the tunnel; 8-B records are not offered for it (api.cpp)
+    constexpr int ELSE = MODE == OUT_REC8 ? kNoChain : INGOT_CHAIN_GENEVE_OVER_V6;
+    const bool known = with_chain<ELSE>(
+        chain, [&](auto c) { go(k_parse<NCH, LAYOUT, decltype(c)::value, MODE, ARGS>); });
+    return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 template <uint32_t NCH, int LAYOUT>

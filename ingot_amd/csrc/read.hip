@@ -116,7 +116,9 @@ __global__ __launch_bounds__(BLOCK) void k_parse_read(ParseArgs a) {
             fr.l3 = NPRE >= 3 && nseg > 4 ? a.len[s0 + 3] : 0u;
         }
         // chunk 0, packet-major: instruction k, lane L fills slot 64k + L =
-        // packet q / CS0, piece (q mod CS0) ^ swz (16-B aligned absolute
+        // packet q / CS0, piece (q mod CS0) ^ swz (walk.h's chunk_of, spelt
+        // out below: through the helper three of the tunnel's field-mode
+        // kernels come out with other registers; 16-B aligned absolute
         // addresses; pieces only below the chunk's end).  Records never read
         // the MAC addresses (the walk reads Ethernet's ethertype only), so, as
         // in k_parse, the window starts at the piece holding chunk 0's byte
@@ -223,25 +225,11 @@ __global__ __launch_bounds__(BLOCK) void k_parse_read(ParseArgs a) {
 template <int CS0, int MODE, bool DENSE = false, int NPRE = 3, bool FIRST = false,
           bool LAZY = false>
 hipError_t launch_read(const ParseArgs& a, int chain, uint32_t g, hipStream_t s) {
-    switch (chain) {
-    case INGOT_CHAIN_UDP_PARSER:
-        hipLaunchKernelGGL((k_parse_read<CS0, INGOT_CHAIN_UDP_PARSER, MODE, DENSE, NPRE, FIRST, LAZY>),
+    // any other tag is the tunnel
+    with_chain<INGOT_CHAIN_GENEVE_OVER_V6>(chain, [&](auto c) {
+        hipLaunchKernelGGL((k_parse_read<CS0, decltype(c)::value, MODE, DENSE, NPRE, FIRST, LAZY>),
                            dim3(g), dim3(BLOCK), 0, s, a);
-        break;
-    case INGOT_CHAIN_GENERIC_ULP:
-        hipLaunchKernelGGL((k_parse_read<CS0, INGOT_CHAIN_GENERIC_ULP, MODE, DENSE, NPRE, FIRST, LAZY>),
-                           dim3(g), dim3(BLOCK), 0, s, a);
-        break;
-    case INGOT_CHAIN_VLAN_ULP:
-        hipLaunchKernelGGL((k_parse_read<CS0, INGOT_CHAIN_VLAN_ULP, MODE, DENSE, NPRE, FIRST, LAZY>),
-                           dim3(g), dim3(BLOCK), 0, s, a);
-        break;
-    default:
-        hipLaunchKernelGGL(
-            (k_parse_read<CS0, INGOT_CHAIN_GENEVE_OVER_V6, MODE, DENSE, NPRE, FIRST, LAZY>), dim3(g),
-            dim3(BLOCK), 0, s, a);
-        break;
-    }
+    });
     return hipGetLastError();
 }
 

@@ -19,55 +19,6 @@ __device__ __forceinline__ uint64_t uniform64(uint64_t v) {
     return ((uint64_t)hi << 32) | lo;
 }
 
-// stage16p (walk.h) with the instruction's immediate offset OFF, which the
-// hardware adds to the source address AND to the LDS destination
-// (k_parse_pipe's 64-B slots: chunk instruction k of a tile is 1 KiB further
-// in both).
-template <int OFF>
-__device__ __forceinline__ void stage16p_at(const uint8_t* src, uint32_t* dst, uint32_t pol) {
-#define INGOT_LD(bits) __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)dst, 16, OFF, bits)
-    switch ((pol >> 6) & 7u) {
-    case 1: INGOT_LD(16); return;
-    case 2: INGOT_LD(18); return;
-    case 3: INGOT_LD(17); return;
-    case 4: INGOT_LD(19); return;
-    case 5: INGOT_LD(1); return;
-    case 6: INGOT_LD(3); return;
-    default:
-        if (pol & 1u) INGOT_LD(2);
-        else INGOT_LD(0);
-    }
-#undef INGOT_LD
-}
-
-// store_rec (walk.h: the same policy bits, the same asm form and s_nop) at a
-// wave-uniform base (SGPR pair) plus a 32-bit per-lane byte offset: no 64-bit
-// address arithmetic per lane.
-#define INGOT_ST(op, bits) asm volatile(op " %0, %1, %2 " bits "\n\ts_nop 1" ::"v"(voff), "v"(x), "s"(base) : "memory")
-#define INGOT_ST_SWITCH(op)                                    \
-    switch ((pol >> 3) & 7u) {                                 \
-    case 1: INGOT_ST(op, "sc1"); return;                       \
-    case 2: INGOT_ST(op, "sc1 nt"); return;                    \
-    case 3: INGOT_ST(op, "sc0 sc1"); return;                   \
-    case 4: INGOT_ST(op, "sc0 sc1 nt"); return;                \
-    case 5: INGOT_ST(op, "sc0"); return;                       \
-    default: if (pol & 2u) { INGOT_ST(op, "nt"); return; }     \
-    }
-__device__ __forceinline__ void store_rec_at(uint8_t* base, uint32_t voff, const uint4& v,
-                                             uint32_t pol) {
-    const u32x4 x{v.x, v.y, v.z, v.w};
-    INGOT_ST_SWITCH("global_store_dwordx4")
-    st_global(reinterpret_cast<uint4*>(base + voff), v);
-}
-__device__ __forceinline__ void store_rec_at(uint8_t* base, uint32_t voff, const uint2& v,
-                                             uint32_t pol) {
-    const u32x2 x{v.x, v.y};
-    INGOT_ST_SWITCH("global_store_dwordx2")
-    st_global(reinterpret_cast<uint2*>(base + voff), v);
-}
-#undef INGOT_ST_SWITCH
-#undef INGOT_ST
-
 // Pipelined variant for fixed slots with no length array (C2-style rings):
 // each wave walks several tiles and keeps the next DEPTH-1 tiles' LDS-DMA in
 // flight while it parses the current one (DEPTH LDS images per wave, used
@@ -79,18 +30,16 @@ __device__ __forceinline__ void store_rec_at(uint8_t* base, uint32_t voff, const
 // (a tree of scalar branches per chunk); 0 = a.policy at run time.
 template <uint32_t NCH, uint32_t DEPTH, int CHAIN, int MODE, uint32_t POL = 0>
 __global__ __launch_bounds__(BLOCK) void k_parse_pipe(ParseArgs a) {
-    constexpr uint32_t WIN = NCH * 16u;
+    using Img = RingImg<NCH, DEPTH>;
     const uint32_t pol = POL ? POL : a.policy;
-    constexpr uint32_t WAVE_DW = WAVE * NCH * 4u;
-    constexpr uint32_t IMG_DW = WAVES * WAVE_DW + 16u;
-    __shared__ __attribute__((aligned(16))) uint32_t s_img[DEPTH * IMG_DW];
+    __shared__ __attribute__((aligned(16))) uint32_t s_img[Img::DW];
     constexpr uint32_t REC_B = MODE == OUT_REC8 ? 8u : 16u;
     const uint32_t lane = threadIdx.x & (WAVE - 1u);
     // wave-uniform (readfirstlane, as in k_parse_ring): the tile cursor, the
     // tile's source and record bases and the loop control stay in SGPRs, and
     // the staging instructions' LDS destinations (M0) are loop constants
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
-    uint32_t* img0 = s_img + wave * WAVE_DW;
+    uint32_t* img0 = s_img + wave * Img::WAVE_DW;
     const uint64_t ntiles = (a.n + WAVE - 1u) / WAVE;
     // only the batch's last tile can hold slots >= n (none if 64 divides n)
     const uint64_t ttail = a.n % WAVE ? ntiles - 1u : ~0ull;
@@ -143,13 +92,12 @@ __global__ __launch_bounds__(BLOCK) void k_parse_pipe(ParseArgs a) {
         constexpr bool S64 = decltype(s64)::value;
         static_assert(!S64 || NCH == 4, "the immediate-offset form is NCH == 4's");
         const uint32_t stride = S64 ? 64u : a.stride;
-        const uint32_t take = stride < WIN ? stride : WIN;
+        const uint32_t take = stride < Img::WIN ? stride : Img::WIN;
         uint32_t voff[NCH];
 #pragma unroll
         for (uint32_t k = 0; k < NCH; ++k) {
-            const uint32_t q = k * WAVE + lane;
-            const uint32_t pp = q / NCH;
-            voff[k] = pp * stride + 16u * ((q - pp * NCH) ^ swz<NCH>(pp));
+            const ChunkOf m = chunk_of<NCH>(k, lane);
+            voff[k] = m.pp * stride + 16u * m.c;
         }
         const uint32_t frame_off = lane * stride;  // the lane's frame in its tile
         const uint32_t rec_off = lane * REC_B;     // and its record
@@ -166,21 +114,16 @@ __global__ __launch_bounds__(BLOCK) void k_parse_pipe(ParseArgs a) {
                 // slots >= n of the tail tile: a valid address (the last slot)
                 uint32_t l = lane;
                 asm volatile("" : "+v"(l));
-#pragma unroll
-                for (uint32_t k = 0; k < NCH; ++k) {
-                    const uint32_t q = k * WAVE + l;
-                    const uint32_t pp = q / NCH;
-                    const uint32_t c = (q - pp * NCH) ^ swz<NCH>(pp);
-                    const uint32_t slot = pp < tail_last ? pp : tail_last;
+                stage_clamped<NCH>(l, 0u, tail_last + 1u, [&](uint32_t k, uint32_t slot, uint32_t c) {
                     stage16p(src + (slot * stride + 16u * c), img + k * WAVE * 4u, pol);
-                }
+                });
             } else if constexpr (S64) {
                 uint32_t vo = voff[0];
                 asm volatile("" : "+v"(vo));
-                stage16p_at<0>(src + vo, img, pol);
-                stage16p_at<1024>(src + vo, img, pol);
-                stage16p_at<2048>(src + vo, img, pol);
-                stage16p_at<3072>(src + vo, img, pol);
+                stage16p<0>(src + vo, img, pol);
+                stage16p<1024>(src + vo, img, pol);
+                stage16p<2048>(src + vo, img, pol);
+                stage16p<3072>(src + vo, img, pol);
             } else {
 #pragma unroll
                 for (uint32_t k = 0; k < NCH; ++k) {
@@ -204,8 +147,8 @@ __global__ __launch_bounds__(BLOCK) void k_parse_pipe(ParseArgs a) {
         // record of tile tt, whose first record is at dst
         auto emit = [&](uint64_t tt, uint8_t* dst, const Rec& r) {
             if (tt == ttail && lane > tail_last) return;
-            if constexpr (MODE == OUT_REC8) store_rec_at(dst, rec_off, pack8(r), pol);
-            else store_rec_at(dst, rec_off, pack(r), pol);
+            if constexpr (MODE == OUT_REC8) store_rec(dst, rec_off, pack8(r), pol);
+            else store_rec(dst, rec_off, pack(r), pol);
         };
 
         const uint8_t* src = a.arena + t * tile_b;  // tile t's first slot
@@ -253,29 +196,21 @@ __global__ __launch_bounds__(BLOCK) void k_parse_pipe(ParseArgs a) {
         // prologue: the first DEPTH-1 tiles
 #pragma unroll
         for (uint32_t d = 0; d + 1u < DEPTH; ++d) {
-            if (ts < tend) stage(ts, ssrc, img0 + d * IMG_DW);
+            if (ts < tend) stage(ts, ssrc, img0 + d * Img::IMG_DW);
             ts += step;
             ssrc += dsrc;
         }
         for (uint32_t j = 0;; ++j) {
             if (ts < tend) {
-                stage(ts, ssrc, img0 + ((j + DEPTH - 1u) % DEPTH) * IMG_DW);
-                // tile j's loads have landed (vector-memory ops retire in
-                // issue order, stores and LDS-DMA alike): younger than them
-                // are the DEPTH-1 later tiles' loads and, once the pipeline
-                // is full, the DEPTH-1 record stores of the tiles before j —
-                // which need not have completed (counting them out left every
-                // tile waiting for the previous record's write-through)
-                if (j + 1u >= DEPTH)
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1u) * (NCH + 1u)) : "memory");
-                else
-                    asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1u) * NCH) : "memory");
+                stage(ts, ssrc, img0 + ((j + DEPTH - 1u) % DEPTH) * Img::IMG_DW);
+                // tile j's loads have landed
+                pipe_wait<NCH, DEPTH>(j + 1u >= DEPTH);
             } else {
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             ts += step;
             ssrc += dsrc;
-            Frame<NCH> fr = frame(t, src, img0 + (j % DEPTH) * IMG_DW);
+            Frame<NCH> fr = frame(t, src, img0 + (j % DEPTH) * Img::IMG_DW);
             Rec r;
             walk<CHAIN, false>(fr, r, nullptr, nullptr);
             emit(t, dst, r);
@@ -318,16 +253,14 @@ __device__ __forceinline__ uint32_t load_system_u32(const uint32_t* p) {
 // the doorbell word >= db_first + b, polled by the wave that needs it.
 template <uint32_t NCH, uint32_t DEPTH, int CHAIN, int MODE>
 __global__ __launch_bounds__(BLOCK) void k_parse_ring(RingArgs a) {
-    constexpr uint32_t WIN = NCH * 16u;
-    constexpr uint32_t WAVE_DW = WAVE * NCH * 4u;
-    constexpr uint32_t IMG_DW = WAVES * WAVE_DW + 16u;
-    __shared__ __attribute__((aligned(16))) uint32_t s_img[DEPTH * IMG_DW];
+    using Img = RingImg<NCH, DEPTH>;
+    __shared__ __attribute__((aligned(16))) uint32_t s_img[Img::DW];
     const uint32_t lane = threadIdx.x & (WAVE - 1u);
     // wave-uniform (readfirstlane): the tile cursors, the batch index and
     // the batch table lookups stay scalar (SGPRs, s_load from the kernel
     // arguments) instead of a per-lane load of the batch pointers per tile
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / WAVE));
-    uint32_t* img0 = s_img + wave * WAVE_DW;
+    uint32_t* img0 = s_img + wave * Img::WAVE_DW;
     const uint32_t tpb = a.tiles_per_batch;
     // Batch groups (RingArgs::groups = G): the grid is cut into G groups of
     // blocks (8 consecutive blocks, one per XCD, per group in turn), group q
@@ -349,7 +282,7 @@ __global__ __launch_bounds__(BLOCK) void k_parse_ring(RingArgs a) {
     uint64_t n = a.n;
     uint32_t stride = a.stride, policy = a.policy, nb = a.nbatches;
     asm volatile("" : "+s"(n), "+s"(stride), "+s"(policy), "+s"(nb));
-    const uint32_t take = stride < WIN ? stride : WIN;
+    const uint32_t take = stride < Img::WIN ? stride : Img::WIN;
     uint32_t avail = a.published;  // batches [0, avail) are known published
     bool live = true;              // false once this wave gave up waiting
 
@@ -412,15 +345,9 @@ __global__ __launch_bounds__(BLOCK) void k_parse_ring(RingArgs a) {
     setb(sc);
     Cur pc = sc;
     auto stage = [&](const Cur& c, uint32_t* img) {
-#pragma unroll
-        for (uint32_t k = 0; k < NCH; ++k) {
-            const uint32_t q = k * WAVE + lane;
-            const uint32_t pp = q / NCH;
-            const uint32_t ch = (q - pp * NCH) ^ swz<NCH>(pp);
-            uint64_t slot = (uint64_t)c.t * WAVE + pp;
-            if (slot >= n) slot = n - 1u;  // a valid address for the tail tile
+        stage_clamped<NCH>(lane, (uint64_t)c.t * WAVE, n, [&](uint32_t k, uint64_t slot, uint32_t ch) {
             stage16p(c.arena + slot * stride + 16u * ch, img + k * WAVE * 4u, policy);
-        }
+        });
     };
     auto parse = [&](const Cur& c, const uint32_t* img) {
         const uint64_t i = (uint64_t)c.t * WAVE + lane;
@@ -441,7 +368,7 @@ __global__ __launch_bounds__(BLOCK) void k_parse_ring(RingArgs a) {
             live = false;
             return false;
         }
-        stage(sc, img0 + (js % DEPTH) * IMG_DW);
+        stage(sc, img0 + (js % DEPTH) * Img::IMG_DW);
         ++js;
         adv(sc);
         return true;
@@ -451,20 +378,15 @@ __global__ __launch_bounds__(BLOCK) void k_parse_ring(RingArgs a) {
 #pragma unroll
     for (uint32_t d = 0; d + 1u < DEPTH; ++d) issue(js);
     for (uint32_t j = 0; j < js; ++j) {
-        // tile j's loads have landed: younger than them are the DEPTH-1 later
-        // tiles' loads and (pipeline full) the DEPTH-1 earlier tiles' record
-        // stores, which may still be in flight (k_parse_pipe)
+        // tile j's loads have landed (a wave that stopped staging drains)
         if (issue(js) && js - j == DEPTH) {
-            if (j + 1u >= DEPTH)
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1u) * (NCH + 1u)) : "memory");
-            else
-                asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1u) * NCH) : "memory");
+            pipe_wait<NCH, DEPTH>(j + 1u >= DEPTH);
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         // the image is restaged only after every lane's reads of it have
         // returned: the record store consumes them (as in k_parse_pipe)
-        parse(pc, img0 + (j % DEPTH) * IMG_DW);
+        parse(pc, img0 + (j % DEPTH) * Img::IMG_DW);
         adv(pc);
     }
 }
@@ -479,25 +401,23 @@ __global__ __launch_bounds__(BLOCK) void k_parse_ring(RingArgs a) {
 template <uint32_t NCH, uint32_t DEPTH, int CHAIN>
 __global__ __launch_bounds__(BLOCK) void k_modify_pipe(ModifyArgs m) {
     const ParseArgs& a = m.p;
-    constexpr uint32_t WIN = NCH * 16u;
-    constexpr uint32_t WAVE_DW = WAVE * NCH * 4u;
-    constexpr uint32_t IMG_DW = WAVES * WAVE_DW + 16u;
-    __shared__ __attribute__((aligned(16))) uint32_t s_img[DEPTH * IMG_DW];
+    using Img = RingImg<NCH, DEPTH>;
+    __shared__ __attribute__((aligned(16))) uint32_t s_img[Img::DW];
     const uint32_t lane = threadIdx.x & (WAVE - 1u);
     const uint32_t wave = threadIdx.x / WAVE;
-    uint32_t* img0 = s_img + wave * WAVE_DW;
+    uint32_t* img0 = s_img + wave * Img::WAVE_DW;
     const uint64_t ntiles = (a.n + WAVE - 1u) / WAVE;
     const uint64_t step = (uint64_t)gridDim.x * WAVES;
     const bool nt_ld = a.policy & 1u;
     uint8_t* arena = const_cast<uint8_t*>(a.arena);
     const uint32_t unit_ch = m.wb / 16u;  // chunks per write-back unit
 
+    // stage_clamped's loop spelt out (through the helper, the DEPTH 2
+    // kernels' register allocation changed); plain stage16: no policy switch
     auto stage = [&](uint64_t tt, uint32_t* img) {
 #pragma unroll
         for (uint32_t k = 0; k < NCH; ++k) {
-            const uint32_t q = k * WAVE + lane;
-            const uint32_t pp = q / NCH;
-            const uint32_t c = (q - pp * NCH) ^ swz<NCH>(pp);
+            const auto [pp, c] = chunk_of<NCH>(k, lane);
             uint64_t slot = tt * WAVE + pp;
             if (slot >= a.n) slot = a.n - 1u;
             stage16(a.arena + slot * a.stride + 16u * c, img + k * WAVE * 4u, nt_ld);
@@ -507,7 +427,7 @@ __global__ __launch_bounds__(BLOCK) void k_modify_pipe(ModifyArgs m) {
         const uint64_t i = tt * WAVE + lane;
         const bool valid = i < a.n;
         uint8_t* frame = arena + (valid ? i : 0) * a.stride;
-        Frame<NCH> fr{(const lds_u32*)img, lane, 0u, WIN, a.stride, frame};
+        Frame<NCH> fr{(const lds_u32*)img, lane, 0u, Img::WIN, a.stride, frame};
         Rec r;
         walk<CHAIN, false>(fr, r, nullptr, nullptr);
         uint32_t dirty = 0;
@@ -534,7 +454,7 @@ __global__ __launch_bounds__(BLOCK) void k_modify_pipe(ModifyArgs m) {
                 for (uint32_t b = 0; b < e.nbytes; ++b) {
                     const uint32_t at = h + e.byte0 + b;
                     const uint8_t x = (uint8_t)(w >> (8u * (e.nbytes - 1u - b)));
-                    if (at < WIN) {
+                    if (at < Img::WIN) {
                         fr.put_staged(at, x);
                         const uint32_t c0 = (at >> 4) & ~(unit_ch - 1u);
                         dirty |= ((1u << unit_ch) - 1u) << c0;
@@ -551,6 +471,9 @@ __global__ __launch_bounds__(BLOCK) void k_modify_pipe(ModifyArgs m) {
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
         for (uint32_t k = 0; k < NCH; ++k) {
+            // chunk_of(k, lane), spelt out: through the helper the compiler
+            // folds the unit's address differently (9 instructions fewer, not
+            // measured)
             const uint32_t q = k * WAVE + lane;
             const uint32_t pp = q / NCH;
             const uint32_t c = (q - pp * NCH) ^ swz<NCH>(pp);
@@ -572,16 +495,17 @@ __global__ __launch_bounds__(BLOCK) void k_modify_pipe(ModifyArgs m) {
     if (t >= ntiles) return;
 #pragma unroll
     for (uint32_t d = 0; d + 1u < DEPTH; ++d)
-        if (t + d * step < ntiles) stage(t + d * step, img0 + d * IMG_DW);
+        if (t + d * step < ntiles) stage(t + d * step, img0 + d * Img::IMG_DW);
     for (uint32_t j = 0;; ++j) {
         const uint64_t tn = t + (DEPTH - 1u) * step;
         if (tn < ntiles) {
-            stage(tn, img0 + ((j + DEPTH - 1u) % DEPTH) * IMG_DW);
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1u) * NCH) : "memory");
+            stage(tn, img0 + ((j + DEPTH - 1u) % DEPTH) * Img::IMG_DW);
+            // the write-back's stores vary per tile: waited out
+            pipe_wait<NCH, DEPTH>(false);
         } else {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        modify(t, img0 + (j % DEPTH) * IMG_DW);
+        modify(t, img0 + (j % DEPTH) * Img::IMG_DW);
         // the write-back's LDS reads are done before this image is restaged
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         t += step;
@@ -589,46 +513,74 @@ __global__ __launch_bounds__(BLOCK) void k_modify_pipe(ModifyArgs m) {
     }
 }
 
-template <uint32_t DEPTH>
-hipError_t launch_modify_pipe(const ModifyArgs& a, int chain, uint32_t grid, hipStream_t s) {
-    switch (chain) {
-    case INGOT_CHAIN_UDP_PARSER:
-        hipLaunchKernelGGL((k_modify_pipe<4, DEPTH, INGOT_CHAIN_UDP_PARSER>), dim3(grid),
-                           dim3(BLOCK), 0, s, a);
-        break;
-    case INGOT_CHAIN_GENERIC_ULP:
-        hipLaunchKernelGGL((k_modify_pipe<4, DEPTH, INGOT_CHAIN_GENERIC_ULP>), dim3(grid),
-                           dim3(BLOCK), 0, s, a);
-        break;
-    case INGOT_CHAIN_VLAN_ULP:
-        hipLaunchKernelGGL((k_modify_pipe<4, DEPTH, INGOT_CHAIN_VLAN_ULP>), dim3(grid),
-                           dim3(BLOCK), 0, s, a);
-        break;
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+// Launch f's kernel for the chain tag (f(integral_constant<int, CHAIN>)).
+template <class F>
+hipError_t launch_for_chain(int chain, F&& f) {
+    return with_chain(chain, f) ? hipGetLastError() : hipErrorInvalidValue;
 }
 
-template <uint32_t NCH, uint32_t DEPTH, int MODE, uint32_t POL = 0>
+template <uint32_t DEPTH>
+hipError_t launch_modify_pipe(const ModifyArgs& a, int chain, uint32_t grid, hipStream_t s) {
+    return launch_for_chain(chain, [&](auto c) {
+        hipLaunchKernelGGL((k_modify_pipe<4, DEPTH, decltype(c)::value>), dim3(grid), dim3(BLOCK),
+                           0, s, a);
+    });
+}
+
+template <uint32_t DEPTH, int MODE, uint32_t POL = 0>
 hipError_t launch_pipe(const ParseArgs& a, int chain, uint32_t grid, hipStream_t s) {
-    switch (chain) {
-    case INGOT_CHAIN_UDP_PARSER:
-        hipLaunchKernelGGL((k_parse_pipe<NCH, DEPTH, INGOT_CHAIN_UDP_PARSER, MODE, POL>),
-                           dim3(grid), dim3(BLOCK), 0, s, a);
-        break;
-    case INGOT_CHAIN_GENERIC_ULP:
-        hipLaunchKernelGGL((k_parse_pipe<NCH, DEPTH, INGOT_CHAIN_GENERIC_ULP, MODE, POL>),
-                           dim3(grid), dim3(BLOCK), 0, s, a);
-        break;
-    case INGOT_CHAIN_VLAN_ULP:
-        hipLaunchKernelGGL((k_parse_pipe<NCH, DEPTH, INGOT_CHAIN_VLAN_ULP, MODE, POL>),
-                           dim3(grid), dim3(BLOCK), 0, s, a);
-        break;
-    default:
-        return hipErrorInvalidValue;
+    return launch_for_chain(chain, [&](auto c) {
+        hipLaunchKernelGGL((k_parse_pipe<4, DEPTH, decltype(c)::value, MODE, POL>), dim3(grid),
+                           dim3(BLOCK), 0, s, a);
+    });
+}
+
+template <uint32_t DEPTH, int MODE>
+hipError_t launch_ring_chain(const RingArgs& a, int chain, uint32_t grid, hipStream_t s) {
+    return launch_for_chain(chain, [&](auto c) {
+        hipLaunchKernelGGL((k_parse_ring<4, DEPTH, decltype(c)::value, MODE>), dim3(grid),
+                           dim3(BLOCK), 0, s, a);
+    });
+}
+
+// The ring kernels' grid over `tiles` 64-slot tiles: INGOT_TUNE_PIPELINE = k
+// > 1 gives every wave k tiles; otherwise a whole number of blocks per CU
+// (`per_cu`: INGOT_TUNE_RING_GRID where the kernel follows it, default 2), so
+// that the tiles spread evenly over the CUs, capped at one tile per wave.
+uint32_t ring_blocks(uint64_t tiles, int pipeline, uint64_t per_cu, uint32_t cus) {
+    uint64_t blocks;
+    if (pipeline > 1) {
+        const uint64_t waves = (tiles + (uint64_t)pipeline - 1) / (uint64_t)pipeline;
+        blocks = (waves + WAVES - 1) / WAVES;
+    } else {
+        const uint64_t cap = per_cu * cus;
+        blocks = (tiles + WAVES - 1) / WAVES;
+        if (blocks > cap) blocks = cap;
     }
-    return hipGetLastError();
+    return (uint32_t)(blocks ? blocks : 1);
+}
+
+// INGOT_TUNE_XCD_REMAP as the kernels' tile-order bits (k_parse_pipe), `mask`
+// the bits the kernel implements: 0 = the default, XCD-major (bit 0; measured,
+// 2 streams 12.22 -> 12.03 us/step at 20 steps, 11.91 -> 11.74
+// at 2,000); 4 = hardware order; 5 = one region per XCD (bit 2, under which
+// bit 0 changes nothing); 1-3 = the bits themselves.
+uint32_t xcd_bits(int v, uint32_t mask) {
+    return (v == 0 ? 1u : v == 4 ? 0u : (uint32_t)v) & mask;
+}
+
+// One depth of launch_slot_ring's ladder.  The default policies (launch_parse:
+// 16-B records 11, 8-B records 3) have their cache bits compiled in at depths
+// 1 and 2 (k_parse_pipe's POL); any other policy, and depths 3 and 4, take
+// the runtime switch.
+template <uint32_t DEPTH>
+hipError_t launch_pipe_depth(const ParseArgs& a, int chain, int mode, uint32_t pg, hipStream_t s) {
+    if constexpr (DEPTH <= 2) {
+        if (mode == OUT_REC16 && a.policy == 11u) return launch_pipe<DEPTH, OUT_REC16, 11u>(a, chain, pg, s);
+        if (mode == OUT_REC8 && a.policy == 3u) return launch_pipe<DEPTH, OUT_REC8, 3u>(a, chain, pg, s);
+    }
+    return mode == OUT_REC8 ? launch_pipe<DEPTH, OUT_REC8>(a, chain, pg, s)
+                            : launch_pipe<DEPTH, OUT_REC16>(a, chain, pg, s);
 }
 
 }  // namespace
@@ -638,61 +590,29 @@ constexpr uint32_t kModifyRingWb = 64;
 constexpr uint32_t kModifyRingPolicy = 3;  // nt staging loads + nt write-back
 
 // C2-style rings (slots >= 64 B, no length array, record output): the
-// multi-tile kernel.  Its grid is a whole number of blocks
-// per CU (default 2), so the tiles spread evenly; measured on MI355X (1 M x
-// 64 B, interleaved A/B): 16.6-16.7 vs 18.6-18.8 us per launch on one
-// stream, 13.5-13.6 vs 14.2-14.4 us per step on two; 6 or 12 tiles per
-// wave (uneven over the CUs) lose most of it.
+// multi-tile kernel k_parse_pipe on ring_blocks' grid (INGOT_TUNE_RING_GRID
+// blocks per CU; 6 or 12 tiles per wave, uneven over the CUs, lose most of
+// what the whole-blocks-per-CU grid gains).
+// Default: one LDS image per wave (DEPTH 1), measured on the two-stream C2
+// schedule against two images, alternated runs of the benchmark's default
+// command: 11.59-11.64 vs 11.87-11.94 us/step
+// (profiles/r07_c2_single_image_ab.json); with the scalar
+// tile loop (round 8, profiles/r08_c2_lean_loop_ab.json) 11.41-11.47 against
+// that parent's 11.61-11.68 us/step, one stream alone 14.00 against 14.9.
+// INGOT_TUNE_PIPE_DEPTH = 2..4 selects that many images (the key's value 1
+// stays EINVAL: the single image is what 0, the default, selects).
 hipError_t launch_slot_ring(const ParseArgs& args, int chain, int mode, const Tuning& t,
                             hipStream_t s) {
     ParseArgs a = args;
-    // tile order: XCD-major by default (measured, DESIGN.md §4.2: 2 streams
-    // 12.22 -> 12.03 us/step at 20 steps, 11.91 -> 11.74 at 2,000);
-    // INGOT_TUNE_XCD_REMAP 4 = hardware order
-    a.xcd_remap = t.xcd_remap == 0   ? 1u
-                  : t.xcd_remap == 4 ? 0u
-                  : t.xcd_remap == 5 ? 4u
-                                     : (uint32_t)t.xcd_remap;
-    const uint64_t tiles = (a.n + WAVE - 1) / WAVE;
-    uint64_t blocks;
-    if (t.pipeline > 1) {
-        const uint64_t waves = (tiles + (uint64_t)t.pipeline - 1) / (uint64_t)t.pipeline;
-        blocks = (waves + WAVES - 1) / WAVES;
-    } else {
-        // blocks per CU: INGOT_TUNE_RING_GRID (as for the ring consumer)
-        const uint64_t cap = (t.ring_grid ? (uint64_t)t.ring_grid : 2ull) * t.cus;
-        blocks = (tiles + WAVES - 1) / WAVES;
-        if (blocks > cap) blocks = cap;
+    a.xcd_remap = xcd_bits(t.xcd_remap, 7u);
+    const uint32_t pg = ring_blocks((a.n + WAVE - 1) / WAVE, t.pipeline,
+                                    t.ring_grid ? (uint64_t)t.ring_grid : 2ull, t.cus);
+    switch (t.pipe_depth) {
+    case 0: return launch_pipe_depth<1>(a, chain, mode, pg, s);
+    case 3: return launch_pipe_depth<3>(a, chain, mode, pg, s);
+    case 4: return launch_pipe_depth<4>(a, chain, mode, pg, s);
+    default: return launch_pipe_depth<2>(a, chain, mode, pg, s);
     }
-    const uint32_t pg = (uint32_t)(blocks ? blocks : 1);
-    // Default: one LDS image per wave (k_parse_pipe DEPTH 1), measured on the
-    // two-stream C2 schedule against two images, alternated runs of the
-    // benchmark's default command: 11.59-11.64 vs 11.87-11.94 us/step
-    // (profiles/r07_c2_single_image_ab.json); a launch on one
-    // stream alone is slower (14.94 vs 14.60 us), INGOT_TUNE_PIPE_DEPTH = 2
-    // brings the second image back (the key's value 1 stays EINVAL: the
-    // single image is what 0, the default, selects).  With the scalar tile
-    // loop (round 8, profiles/r08_c2_lean_loop_ab.json): 11.41-11.47 against
-    // the parent's 11.61-11.68 us/step, one stream alone 14.00 against 14.9.
-    if (t.pipe_depth == 0) {
-        // the default policies compiled in, as below
-        if (mode == OUT_REC16 && a.policy == 11u) return launch_pipe<4, 1, OUT_REC16, 11u>(a, chain, pg, s);
-        if (mode == OUT_REC8 && a.policy == 3u) return launch_pipe<4, 1, OUT_REC8, 3u>(a, chain, pg, s);
-        return mode == OUT_REC8 ? launch_pipe<4, 1, OUT_REC8>(a, chain, pg, s)
-                                : launch_pipe<4, 1, OUT_REC16>(a, chain, pg, s);
-    }
-    if (t.pipe_depth == 3)
-        return mode == OUT_REC8 ? launch_pipe<4, 3, OUT_REC8>(a, chain, pg, s)
-                                : launch_pipe<4, 3, OUT_REC16>(a, chain, pg, s);
-    if (t.pipe_depth == 4)
-        return mode == OUT_REC8 ? launch_pipe<4, 4, OUT_REC8>(a, chain, pg, s)
-                                : launch_pipe<4, 4, OUT_REC16>(a, chain, pg, s);
-    // the default policies (launch_parse: 16-B records 11, 8-B records 3)
-    // with their cache bits compiled in
-    if (mode == OUT_REC16 && a.policy == 11u) return launch_pipe<4, 2, OUT_REC16, 11u>(a, chain, pg, s);
-    if (mode == OUT_REC8 && a.policy == 3u) return launch_pipe<4, 2, OUT_REC8, 3u>(a, chain, pg, s);
-    return mode == OUT_REC8 ? launch_pipe<4, 2, OUT_REC8>(a, chain, pg, s)
-                            : launch_pipe<4, 2, OUT_REC16>(a, chain, pg, s);
 }
 
 // Slot rings (slots >= 64 B, no length array): the multi-tile kernel with
@@ -701,43 +621,12 @@ hipError_t launch_slot_ring(const ParseArgs& args, int chain, int mode, const Tu
 hipError_t launch_modify_ring(const ModifyArgs& args, int chain, const Tuning& t,
                               hipStream_t s) {
     ModifyArgs a = args;
-    a.p.xcd_remap = t.xcd_remap == 0 ? 1u : t.xcd_remap == 4 ? 0u : ((uint32_t)t.xcd_remap & 1u);
+    a.p.xcd_remap = xcd_bits(t.xcd_remap, 1u);  // block order only
     a.wb = t.writeback ? (uint32_t)t.writeback : kModifyRingWb;
     a.p.policy = t.cache_policy ? (uint32_t)t.cache_policy & 0x3bu : kModifyRingPolicy;
-    const uint64_t tiles = (a.p.n + WAVE - 1) / WAVE;
-    uint64_t blocks;
-    if (t.pipeline > 1) {
-        const uint64_t waves = (tiles + (uint64_t)t.pipeline - 1) / (uint64_t)t.pipeline;
-        blocks = (waves + WAVES - 1) / WAVES;
-    } else {
-        const uint64_t cap = 2ull * t.cus;
-        blocks = (tiles + WAVES - 1) / WAVES;
-        if (blocks > cap) blocks = cap;
-    }
-    const uint32_t pg = (uint32_t)(blocks ? blocks : 1);
+    const uint32_t pg = ring_blocks((a.p.n + WAVE - 1) / WAVE, t.pipeline, 2, t.cus);
     return t.pipe_depth == 3 ? launch_modify_pipe<3>(a, chain, pg, s)
                              : launch_modify_pipe<2>(a, chain, pg, s);
-}
-
-template <uint32_t DEPTH, int MODE>
-hipError_t launch_ring_chain(const RingArgs& a, int chain, uint32_t grid, hipStream_t s) {
-    switch (chain) {
-    case INGOT_CHAIN_UDP_PARSER:
-        hipLaunchKernelGGL((k_parse_ring<4, DEPTH, INGOT_CHAIN_UDP_PARSER, MODE>), dim3(grid),
-                           dim3(BLOCK), 0, s, a);
-        break;
-    case INGOT_CHAIN_GENERIC_ULP:
-        hipLaunchKernelGGL((k_parse_ring<4, DEPTH, INGOT_CHAIN_GENERIC_ULP, MODE>), dim3(grid),
-                           dim3(BLOCK), 0, s, a);
-        break;
-    case INGOT_CHAIN_VLAN_ULP:
-        hipLaunchKernelGGL((k_parse_ring<4, DEPTH, INGOT_CHAIN_VLAN_ULP, MODE>), dim3(grid),
-                           dim3(BLOCK), 0, s, a);
-        break;
-    default:
-        return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
 }
 
 // The ring consumer's grid is persistent: blocks per CU x CUs (default 2,
@@ -749,11 +638,8 @@ hipError_t launch_ring(const RingArgs& args, int chain, int mode, const Tuning& 
     if (a.nbatches == 0 || a.n == 0) return hipSuccess;
     if (t.cache_policy == 0) a.policy = mode == OUT_REC16 ? 11u : 3u;
     else a.policy = (uint32_t)t.cache_policy & 0x1fbu;
-    const uint64_t total = (uint64_t)a.tiles_per_batch * a.nbatches;
-    const uint64_t bpc = t.ring_grid ? (uint64_t)t.ring_grid : 2ull;
-    uint64_t blocks = (total + WAVES - 1) / WAVES;
-    if (blocks > bpc * t.cus) blocks = bpc * t.cus;
-    const uint32_t g = (uint32_t)(blocks ? blocks : 1);
+    const uint32_t g = ring_blocks((uint64_t)a.tiles_per_batch * a.nbatches, 0,
+                                   t.ring_grid ? (uint64_t)t.ring_grid : 2ull, t.cus);
     // batch groups only on a grid of whole 8-block rows per group
     a.groups = t.ring_groups > 1 ? (uint32_t)t.ring_groups : 1u;
     if (g % (8u * a.groups) != 0 || a.groups > a.nbatches) a.groups = 1;

@@ -54,9 +54,7 @@ __global__ __launch_bounds__(BLOCK, 8) void k_flows_bits(FlowArgs args) {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
         for (uint32_t k = 0; k < NCH; ++k) {
-            const uint32_t q = k * WAVE + lane;
-            const uint32_t pp = q / NCH;
-            const uint32_t c = (q - pp * NCH) ^ swz<NCH>(pp);
+            const auto [pp, c] = chunk_of<NCH>(k, lane);
             const uint32_t np = (uint32_t)__shfl((int)nch, (int)pp);
             const int64_t bp = (int64_t)__shfl((long long)base, (int)pp);
             if (c < np) stage16(a.arena + bp + 16u * c, wimg + k * WAVE * 4u, false);
@@ -86,20 +84,10 @@ __global__ __launch_bounds__(BLOCK, 8) void k_flows_bits(FlowArgs args) {
 
 template <uint32_t NCH>
 hipError_t go_bits(const FlowArgs& a, int chain, uint32_t g, hipStream_t s) {
-    switch (chain) {
-    case INGOT_CHAIN_UDP_PARSER:
-        hipLaunchKernelGGL((k_flows_bits<NCH, INGOT_CHAIN_UDP_PARSER>), dim3(g),
-                           dim3(BLOCK), 0, s, a);
-        break;
-    case INGOT_CHAIN_GENERIC_ULP:
-        hipLaunchKernelGGL((k_flows_bits<NCH, INGOT_CHAIN_GENERIC_ULP>), dim3(g),
-                           dim3(BLOCK), 0, s, a);
-        break;
-    default:
-        hipLaunchKernelGGL((k_flows_bits<NCH, INGOT_CHAIN_VLAN_ULP>), dim3(g),
-                           dim3(BLOCK), 0, s, a);
-        break;
-    }
+    // (launch_flows sends the tunnel elsewhere: any other tag is VlanUlp)
+    with_chain<INGOT_CHAIN_VLAN_ULP>(chain, [&](auto c) {
+        hipLaunchKernelGGL((k_flows_bits<NCH, decltype(c)::value>), dim3(g), dim3(BLOCK), 0, s, a);
+    });
     return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // walk.h — the device side shared by the parse kernels (parse.hip,
-// read.hip, ring.hip): LDS-DMA staging and record stores, the lane's frame
+// read.hip, ring.hip, tuple.hip): LDS-DMA staging and record stores, the
+// staging map and the ring kernels' shared pieces, the lane's frame
 // views (Frame, SegFrameP), the chain walk `walk<CHAIN>()` that
 // restates ingot's generated parse_slice / parse_read (see parse.hip's
 // header for the reference map), the setters' and the flow hash's helpers,
@@ -53,8 +54,12 @@ __device__ __forceinline__ void stage16(const uint8_t* src, uint32_t* dst, bool 
 // The same with the policy word: bits 6-8, when non-zero, pick the staging
 // loads' cache bits instead of bit 0 (1 sc1, 2 sc1 nt, 3 sc0 sc1, 4 sc0 sc1
 // nt, 5 sc0, 6 sc0 nt) — A/B of where the frame lines are allocated.
+// OFF: the instruction's immediate offset, which the hardware adds to the
+// source address AND to the LDS destination (k_parse_pipe's 64-B slots: chunk
+// instruction k of a tile is 1 KiB further in both).
+template <int OFF = 0>
 __device__ __forceinline__ void stage16p(const uint8_t* src, uint32_t* dst, uint32_t pol) {
-#define INGOT_LD(bits) __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)dst, 16, 0, bits)
+#define INGOT_LD(bits) __builtin_amdgcn_global_load_lds((const void*)src, (lds_void*)dst, 16, OFF, bits)
     switch ((pol >> 6) & 7u) {
     case 1: INGOT_LD(16); return;
     case 2: INGOT_LD(18); return;
@@ -87,25 +92,41 @@ __device__ __forceinline__ void st_global(uint4* dst, const uint4& v) {
 __device__ __forceinline__ void st_global(uint2* dst, const uint2& v) {
     *(__attribute__((address_space(1))) u32x2*)dst = u32x2{v.x, v.y};
 }
-#define INGOT_ST(op, bits) asm volatile(op " %0, %1, off " bits "\n\ts_nop 1" ::"v"(dst), "v"(x) : "memory")
-#define INGOT_ST_SWITCH(op)                                    \
-    switch ((pol >> 3) & 7u) {                                 \
-    case 1: INGOT_ST(op, "sc1"); return;                       \
-    case 2: INGOT_ST(op, "sc1 nt"); return;                    \
-    case 3: INGOT_ST(op, "sc0 sc1"); return;                   \
-    case 4: INGOT_ST(op, "sc0 sc1 nt"); return;                \
-    case 5: INGOT_ST(op, "sc0"); return;                       \
-    default: if (pol & 2u) { INGOT_ST(op, "nt"); return; }     \
+// `addr`: the instruction's address and data operands as written, the asm
+// inputs after it — a per-lane pointer ("%0, %1, off"), or a wave-uniform base
+// (SGPR pair) plus a 32-bit per-lane byte offset ("%0, %1, %2": no 64-bit
+// address arithmetic per lane).
+#define INGOT_ST(op, bits, addr, ...) asm volatile(op " " addr " " bits "\n\ts_nop 1" ::__VA_ARGS__ : "memory")
+#define INGOT_ST_SWITCH(op, ...)                                            \
+    switch ((pol >> 3) & 7u) {                                              \
+    case 1: INGOT_ST(op, "sc1", __VA_ARGS__); return;                       \
+    case 2: INGOT_ST(op, "sc1 nt", __VA_ARGS__); return;                    \
+    case 3: INGOT_ST(op, "sc0 sc1", __VA_ARGS__); return;                   \
+    case 4: INGOT_ST(op, "sc0 sc1 nt", __VA_ARGS__); return;                \
+    case 5: INGOT_ST(op, "sc0", __VA_ARGS__); return;                       \
+    default: if (pol & 2u) { INGOT_ST(op, "nt", __VA_ARGS__); return; }     \
     }
 __device__ __forceinline__ void store_rec(uint4* dst, const uint4& v, uint32_t pol) {
     const u32x4 x{v.x, v.y, v.z, v.w};
-    INGOT_ST_SWITCH("global_store_dwordx4")
+    INGOT_ST_SWITCH("global_store_dwordx4", "%0, %1, off", "v"(dst), "v"(x))
     st_global(dst, v);
 }
 __device__ __forceinline__ void store_rec(uint2* dst, const uint2& v, uint32_t pol) {
     const u32x2 x{v.x, v.y};
-    INGOT_ST_SWITCH("global_store_dwordx2")
+    INGOT_ST_SWITCH("global_store_dwordx2", "%0, %1, off", "v"(dst), "v"(x))
     st_global(dst, v);
+}
+__device__ __forceinline__ void store_rec(uint8_t* base, uint32_t voff, const uint4& v,
+                                          uint32_t pol) {
+    const u32x4 x{v.x, v.y, v.z, v.w};
+    INGOT_ST_SWITCH("global_store_dwordx4", "%0, %1, %2", "v"(voff), "v"(x), "s"(base))
+    st_global(reinterpret_cast<uint4*>(base + voff), v);
+}
+__device__ __forceinline__ void store_rec(uint8_t* base, uint32_t voff, const uint2& v,
+                                          uint32_t pol) {
+    const u32x2 x{v.x, v.y};
+    INGOT_ST_SWITCH("global_store_dwordx2", "%0, %1, %2", "v"(voff), "v"(x), "s"(base))
+    st_global(reinterpret_cast<uint2*>(base + voff), v);
 }
 #undef INGOT_ST_SWITCH
 #undef INGOT_ST
@@ -114,16 +135,57 @@ __device__ __forceinline__ void store_rec(uint2* dst, const uint2& v, uint32_t p
 // NCH = 4: g(p) = (p>>2)&3; NCH = 8: g(p) = (p>>1)&7 (see header comment);
 // other NCH: linear.
 template <uint32_t NCH>
-__device__ __forceinline__ uint32_t swz(uint32_t p) {
+__host__ __device__ __forceinline__ constexpr uint32_t swz(uint32_t p) {
     if constexpr (NCH == 4) return (p >> 2) & 3u;
     else if constexpr (NCH == 8) return (p >> 1) & 7u;
     else return 0u;
 }
 
 template <uint32_t NCH>
-__device__ __forceinline__ uint32_t slot_of(uint32_t p, uint32_t c) {
+__host__ __device__ __forceinline__ constexpr uint32_t slot_of(uint32_t p, uint32_t c) {
     return NCH * p + (c ^ swz<NCH>(p));
 }
+
+// The staging map, slot_of's inverse.  LDS-DMA fills the image lane-linearly:
+// staging instruction k (of NCH per tile), lane L writes unit q = 64k + L,
+// which must hold chunk c of packet pp with slot_of(pp, c) == q — so that lane
+// fetches that chunk.  (NCH = 0, k_parse without staging: never called at
+// run time, compiled as NCH = 1.)  The arguments come by reference: by value
+// they are `noundef`, from which the compiler narrows the division by a
+// non-power-of-two NCH to 16 bits — other instructions in k_parse and
+// k_flows_bits than the ones their measurements were taken with.
+// Two sites still spell the map out, because going through chunk_of changed
+// their kernels' instructions ("One copy of the shared
+// helpers"): k_parse_read's staging loop and k_modify_pipe's write-back.
+struct ChunkOf {
+    uint32_t pp, c;  // packet within the tile, chunk within its window
+};
+template <uint32_t NCH>
+__host__ __device__ __forceinline__ constexpr ChunkOf chunk_of(const uint32_t& k,
+                                                               const uint32_t& lane) {
+    constexpr uint32_t N = NCH ? NCH : 1u;
+    const uint32_t q = k * WAVE + lane;
+    const uint32_t pp = q / N;
+    return ChunkOf{pp, (q - pp * N) ^ swz<NCH>(pp)};
+}
+// chunk_of and slot_of agree on every unit of the image; the units are the
+// 64 * NCH distinct values 64k + L and every (pp, c) is in range, so the map
+// is a bijection onto [0, 64 * NCH).
+template <uint32_t NCH>
+constexpr bool staging_map_ok() {
+    for (uint32_t k = 0; k < NCH; ++k)
+        for (uint32_t lane = 0; lane < WAVE; ++lane) {
+            const ChunkOf m = chunk_of<NCH>(k, lane);
+            if (m.pp >= WAVE || m.c >= NCH || slot_of<NCH>(m.pp, m.c) != k * WAVE + lane)
+                return false;
+        }
+    return true;
+}
+// every window size a kernel is instantiated with
+static_assert(staging_map_ok<2>() && staging_map_ok<3>() && staging_map_ok<4>() &&
+                  staging_map_ok<5>() && staging_map_ok<6>() && staging_map_ok<8>() &&
+                  staging_map_ok<9>(),
+              "the staging map and Frame::dw's slot_of disagree");
 
 // One lane's view of its frame: LDS window for the first bytes, HBM beyond.
 template <uint32_t NCH>
@@ -1150,6 +1212,81 @@ __device__ __forceinline__ bool flow_hash(const FR& f, const Rec& r, const uint3
     if constexpr (H16) h = ok ? toeplitz9_16(x, tab) : 0u;
     else h = ok ? toeplitz9(x, tab) : 0u;
     return ok;
+}
+
+// ---------------------------------------------------------------------------
+// The ring kernels' shared pieces (ring.hip: k_parse_pipe, k_parse_ring,
+// k_modify_pipe).
+// ---------------------------------------------------------------------------
+// Their LDS: DEPTH image sets, each the block's four wave images of 64 x NCH
+// 16-B units, `uint32_t s_img[RingImg<NCH, DEPTH>::DW]`.  The 16 dwords after
+// a set date from when a speculated second dword of a pair could be read past
+// a packet's slots; Frame::be clamps it now and k_parse dropped its slack
+// (measured neutral), but here the 64 B stay: they are in the footprint
+// every ring measurement was taken at (16,448 B per set at NCH = 4).
+template <uint32_t NCH, uint32_t DEPTH>
+struct RingImg {
+    static constexpr uint32_t WIN = NCH * 16u;                 // bytes staged per slot
+    static constexpr uint32_t WAVE_DW = WAVE * NCH * 4u;       // dwords per wave image
+    static constexpr uint32_t IMG_DW = WAVES * WAVE_DW + 16u;  // dwords per set
+    static constexpr uint32_t DW = DEPTH * IMG_DW;
+};
+
+// Staging addresses of a tile that may reach past the batch's end: chunk
+// instruction k's lane gets slot `first + pp`, and slots at or beyond `n` take
+// the last slot's (a valid address; their lanes' records are not stored).
+// ld(k, slot, c) issues the load of chunk c of that slot.  (By reference: as
+// chunk_of.)
+template <uint32_t NCH, class T, class LD>
+__device__ __forceinline__ void stage_clamped(const uint32_t& lane, const T& first, const T& n,
+                                              LD ld) {
+#pragma unroll
+    for (uint32_t k = 0; k < NCH; ++k) {
+        const ChunkOf m = chunk_of<NCH>(k, lane);
+        T slot = first + m.pp;
+        if (slot >= n) slot = n - 1u;
+        ld(k, slot, m.c);
+    }
+}
+
+// The wait for the oldest of DEPTH staged tiles, right after the youngest was
+// issued.  Vector-memory operations retire in issue order, stores and LDS-DMA
+// alike: younger than the oldest tile's NCH loads are the DEPTH-1 later
+// tiles' loads and, once the pipeline is full (`stores`), the DEPTH-1 record
+// stores of the tiles before it — one per tile, which need not have completed
+// (counting them out left every tile waiting for the previous record's
+// write-through).  A kernel whose stores per tile vary passes false and waits
+// them out.
+template <uint32_t NCH, uint32_t DEPTH>
+__device__ __forceinline__ void pipe_wait(bool stores) {
+    if (stores) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1u) * (NCH + 1u)) : "memory");
+    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"((DEPTH - 1u) * NCH) : "memory");
+}
+
+// Host side: f(std::integral_constant<int, CHAIN>{}) for the chain tag, so a
+// launcher names its kernel once.  ELSE: the chain every other tag runs as
+// (the launchers that also instantiate the tunnel chain pass it; api.cpp has
+// checked the tag); none: false for an unknown tag.
+constexpr int kNoChain = -1;
+template <int ELSE = kNoChain, class F>
+bool with_chain(int chain, F&& f) {
+    switch (chain) {
+    case INGOT_CHAIN_UDP_PARSER:
+        f(std::integral_constant<int, INGOT_CHAIN_UDP_PARSER>{});
+        return true;
+    case INGOT_CHAIN_GENERIC_ULP:
+        f(std::integral_constant<int, INGOT_CHAIN_GENERIC_ULP>{});
+        return true;
+    case INGOT_CHAIN_VLAN_ULP:
+        f(std::integral_constant<int, INGOT_CHAIN_VLAN_ULP>{});
+        return true;
+    default:
+        if constexpr (ELSE != kNoChain) {
+            f(std::integral_constant<int, ELSE>{});
+            return true;
+        }
+        return false;
+    }
 }
 
 // Blocks of `kernel` one CU holds at once (its LDS / VGPR footprint), queried

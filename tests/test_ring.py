@@ -66,6 +66,37 @@ def test_ring_bit_exact(torch, grid, depth, pol, groups, n):
                 assert o8.cpu().numpy().tobytes() == ingot_amd.rec16_to_rec8(want).tobytes()
 
 
+@pytest.mark.parametrize("n,tpw,remap", [(1601, 9, 0), (12225, 6, 2), (12225, 6, 5)])
+@pytest.mark.parametrize("pol", [4, 75])
+def test_slot_ring_two_images_runtime_policy(torch, n, tpw, remap, pol):
+    """The single-batch slot-ring kernel with two LDS images per wave
+    (INGOT_TUNE_PIPE_DEPTH 2) and a cache policy other than the two compiled
+    into it (4: plain loads and stores; 75: sc1 loads and stores with the nt
+    bits), i.e. its runtime policy switch — the one rung of the slot-ring
+    launcher's ladder no other test reaches.  1,601 frames at 9 tiles per wave:
+    one block, every wave 6 tiles or more (the pipeline fills), one valid lane
+    in the tail tile.  12,225 frames at 6 tiles per wave: 192 tiles on 8
+    blocks, the grid the contiguous-run (2) and per-XCD-region (5) tile orders
+    need.  64-B slots (immediate-offset staging) and 80-B slots (per-lane
+    offsets); records equal the oracle's."""
+    from ingot_amd.abi import TUNE_PIPELINE, TUNE_XCD_REMAP
+
+    ctx = ingot_amd.Context(0)
+    ctx.set_tuning(TUNE_PIPE_DEPTH, 2)
+    ctx.set_tuning(TUNE_CACHE_POLICY, pol)
+    ctx.set_tuning(TUNE_PIPELINE, tpw)
+    ctx.set_tuning(TUNE_XCD_REMAP, remap)
+    for prof, stride in ((GenProfile.ADVERSARIAL, 64), (GenProfile.MIXED, 80)):
+        arena = ingot_amd.gen_frames(prof, n, seed=n + pol, stride=stride)[0]
+        for chain in (Chain.UdpParser, Chain.GenericUlp, Chain.VlanUlp):
+            want = _want(arena, chain, stride, n)
+            got = ctx.parse_strided(arena, stride, n, chain)
+            got8 = ctx.parse_strided_compact(arena, stride, n, chain)
+            torch.cuda.synchronize()
+            assert got.cpu().numpy().tobytes() == want.tobytes(), (prof, chain)
+            assert got8.cpu().numpy().tobytes() == ingot_amd.rec16_to_rec8(want).tobytes()
+
+
 def test_ring_equals_per_batch_launches_and_aliased_batches(torch):
     """A batch list may name the same arena twice (the bench rotates copies);
     every batch's records equal a single-batch parse of its arena."""
