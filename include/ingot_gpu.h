@@ -38,11 +38,12 @@
 extern "C" {
 #endif
 
-/* 3: ingot_gpu_comm_wrap (borrow the host's RCCL communicator).
+/* 4: ingot_gpu_checksum_verify / ingot_gpu_checksum_fill (ingot_csum).
+ * 3: ingot_gpu_comm_wrap (borrow the host's RCCL communicator).
  * 2: ingot_gpu_comm_* / ingot_gpu_flow_hist_allreduce (config 5's reduce);
  *    host mappings counted per map, ingot_gpu_host_unmap EINVAL for a pointer
  *    the context never mapped (1: any pointer, hipHostUnregister'd). */
-#define INGOT_GPU_ABI_VERSION 3
+#define INGOT_GPU_ABI_VERSION 4
 
 /* ---------------------------------------------------------------------------
  * Per-packet status: 0 = Ok, else 1 + the ParseError discriminant in the
@@ -860,6 +861,94 @@ int ingot_gpu_emit_headers(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_
                            const ingot_emit_set* sets, uint32_t n_sets,
                            const uint16_t* d_len, uint64_t n, uint8_t* d_out,
                            const uint64_t* d_out_off, uint32_t out_stride, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Internet checksums (RFC 1071) of already parsed frames: verify or fill the
+ * IPv4 header checksum and the TCP / UDP / ICMPv4 / ICMPv6 checksum of every
+ * packet of a batch, on the device.  Build-defined, like the flow hash: ingot
+ * has no checksum code and leaves the sums to its caller (OPTE computes them
+ * on the CPU, per packet); tests/csum_model.py is the definition.
+ *
+ * Frames as in ingot_gpu_fields (d_off NULL selects slots of `stride`, a
+ * multiple of 16 in a 16-B aligned arena, and d_len NULL then means `stride`;
+ * with d_off the arena may have any alignment); reads stay inside each
+ * frame's 16-byte blocks.  d_rec holds the 16-B records of an earlier parse
+ * of the same frames, under any chain: the layers are taken from the record's
+ * l3_kind, l4_kind, l3_off, l4_off, payload_off, l4_proto and n_v6ext (for a
+ * GENEVE_OVER_V6 record these are the inner layers; the outer checksums of a
+ * tunnel frame come from a UDP_PARSER parse of it).  `what` selects the layers
+ * (INGOT_CSUM_L3 | INGOT_CSUM_L4; 0 or any other bit: EINVAL); a layer that
+ * is not selected reports NONE and zeros.
+ *
+ * Only records with status Ok are processed; all others, and records whose
+ * offsets do not fit their frame (l3_off + the fixed L3 header <= l4_off,
+ * l4_off + the smallest L4 header (TCP 20, UDP 8, ICMP 8) <= payload_off <=
+ * the frame length), give NONE / NONE and zeros.
+ *   L3   IPv4 only (IPv6 has no header sum: NONE), over the bytes ingot parsed
+ *        as the header, max(20, ihl * 4), which must end inside the frame
+ *        (else NONE).  OK iff the folded ones'-complement sum including the
+ *        field is 0xffff, else BAD; l3_sum is the complement of the sum with
+ *        the field taken as 0.
+ *   L4   the segment is [l4_off, end), end = l3_off + total_len (IPv4) or
+ *        l3_off + 40 + payload_len (IPv6); frame bytes past `end` (Ethernet
+ *        padding) are not summed.  In this order:
+ *          SHORT     iff end > the frame length or end < payload_off;
+ *          FRAGMENT  IPv4: MF set or fragment offset != 0; IPv6: one of the
+ *                    n_v6ext extension headers, walked from l3_off + 40 (a
+ *                    Fragment header, selected by the value 44, is 8 bytes, any
+ *                    other 8 + 8 * its length byte), is a Fragment header with
+ *                    offset != 0 or M = 1 (an atomic fragment is summed);
+ *          ZERO      verify, UDP only (IPv4 and IPv6 alike): the field is 0.
+ *                    l4_sum is still computed; whether a zero sum is allowed
+ *                    (RFC 6935) is the caller's decision;
+ *          OK / BAD  as for L3, over the pseudo-header and the segment (an odd
+ *                    last byte padded with 0).
+ *        Pseudo-header: ICMPv4 none; over IPv4 (TCP, UDP; also an ICMPv6
+ *        layer) source, destination, 0, the header's protocol byte and the
+ *        16-bit segment length; over IPv6 (TCP, UDP, ICMPv6) source,
+ *        destination, the 32-bit segment length and rec.l4_proto (RFC 8200
+ *        8.1).  l4_sum is the complement of the sum with the field taken as
+ *        0, for UDP given as 0xffff when that is 0 (RFC 768); l4_len the
+ *        segment's bytes.  SHORT and FRAGMENT rows carry zeros.
+ *
+ * ingot_gpu_checksum_fill writes exactly the two checksum bytes of every
+ * layer that verify would report OK, BAD or ZERO (l3_sum / l4_sum, big-
+ * endian) and nothing else, and reports the state after writing (OK) in
+ * d_out, which may be NULL.  UDP is always computed.  A caller that fills
+ * both levels of a tunnel frame runs the inner call first, then the outer, on
+ * one stream.  Frames of one call must not overlap.
+ * ------------------------------------------------------------------------- */
+enum ingot_csum_state {
+    INGOT_CSUM_NONE = 0,     /* nothing to check: record not Ok, no such layer, IPv6 (no header sum) */
+    INGOT_CSUM_OK = 1,
+    INGOT_CSUM_BAD = 2,
+    INGOT_CSUM_ZERO = 3,     /* L4, UDP only: the field is 0, the sender computed none */
+    INGOT_CSUM_SHORT = 4,    /* L4: the L3 header's length ends past the frame or inside the L4 header */
+    INGOT_CSUM_FRAGMENT = 5  /* L4: the packet is a fragment; not summed */
+};
+#define INGOT_CSUM_L3 1u
+#define INGOT_CSUM_L4 2u
+
+typedef struct ingot_csum {
+    uint8_t l3_state;  /* enum ingot_csum_state */
+    uint8_t l4_state;
+    uint16_t l3_sum;   /* the value the IPv4 checksum field must carry */
+    uint16_t l4_sum;   /* the value the L4 checksum field must carry (UDP: 0 is given as 0xffff) */
+    uint16_t l4_len;   /* bytes of the L4 segment that were summed */
+} ingot_csum;
+
+#ifdef __cplusplus
+static_assert(sizeof(ingot_csum) == 8, "ingot_csum is 8 bytes");
+#endif
+
+int ingot_gpu_checksum_verify(ingot_gpu_ctx* ctx, const uint8_t* d_arena,
+                              const uint64_t* d_off, const uint16_t* d_len,
+                              uint32_t stride, uint64_t n, const ingot_rec* d_rec,
+                              uint32_t what, ingot_csum* d_out, void* stream);
+int ingot_gpu_checksum_fill(ingot_gpu_ctx* ctx, uint8_t* d_arena,
+                            const uint64_t* d_off, const uint16_t* d_len,
+                            uint32_t stride, uint64_t n, const ingot_rec* d_rec,
+                            uint32_t what, ingot_csum* d_out, void* stream);
 
 /*
  * Flow classification + per-flow histogram (config 5; build-defined, ingot

@@ -23,6 +23,12 @@ from . import _lib
 from .abi import (  # noqa: F401  (re-exports)
     ABI_VERSION,
     CHAIN_LABELS,
+    CSUM_BYTES,
+    CSUM_DTYPE,
+    CSUM_L3,
+    CSUM_L4,
+    CsumState,
+    IngotCsum,
     FIELDS_BYTES,
     FIELDS_DTYPE,
     GEN_SEED,
@@ -59,7 +65,7 @@ __all__ = [
     "Chain", "Context", "GenProfile", "PacketParseError", "ParseError", "UdpParser",
     "GenericUlp", "VlanUlp", "GeneveOverV6Tunnel", "gen_frames", "gen_lengths", "records_to_numpy",
     "fields_to_numpy", "load_library", "Parsed", "chunk_tables", "HeaderKind", "parse_header",
-    "HeaderParseError", "first_chunks",
+    "HeaderParseError", "first_chunks", "CsumState", "CSUM_L3", "CSUM_L4", "CSUM_DTYPE",
 ]
 
 
@@ -538,6 +544,44 @@ class Context:
             _ptr(lens), n, _ptr(out), _ptr(out_off), int(stride), _stream(stream, self.device)),
             "ingot_gpu_emit_headers")
         return out
+
+    def _checksum(self, name: str, arena, off, lens, recs, what: int, stride: int,
+                  n: Optional[int], out, stream):
+        if n is None:
+            n = off.numel() if off is not None else recs.numel() // REC_BYTES
+        if int(what) == 0 or int(what) & ~(CSUM_L3 | CSUM_L4):
+            raise ValueError("what must be CSUM_L3, CSUM_L4 or both")
+        self._frames(arena, off, lens, stride, n)
+        self._arg("recs", recs, _U8, n * REC_BYTES)
+        self._arg("out", out, _U8, n * CSUM_BYTES, optional=True)
+        self._on_device(arena=arena, off=off, lens=lens, recs=recs, out=out)
+        fn = getattr(self._lib, name)
+        _lib.check(fn(self._h, _ptr(arena), _ptr(off), _ptr(lens), int(stride), n, _ptr(recs),
+                      int(what), _ptr(out), _stream(stream, self.device)), name)
+        return out
+
+    def checksum_verify(self, arena, off, lens, recs, what: int = CSUM_L3 | CSUM_L4,
+                        stride: int = 0, n: Optional[int] = None, out=None, stream=None):
+        """ingot_gpu_checksum_verify: the IPv4 header (CSUM_L3) and TCP / UDP /
+        ICMP (CSUM_L4) checksums of frames already parsed into `recs` ((n, 16)
+        uint8 ingot_rec records, any chain).  Frames as in fields(): off/lens,
+        or off=None for slots of `stride`.  Returns an (n, 8) uint8 tensor of
+        ingot_csum rows (CSUM_DTYPE)."""
+        if out is None:
+            if n is None:
+                n = off.numel() if off is not None else recs.numel() // REC_BYTES
+            out = _torch().empty((n, CSUM_BYTES), dtype=_torch().uint8, device=arena.device)
+        return self._checksum("ingot_gpu_checksum_verify", arena, off, lens, recs, what, stride,
+                              n, out, stream)
+
+    def checksum_fill(self, arena, off, lens, recs, what: int = CSUM_L3 | CSUM_L4,
+                      stride: int = 0, n: Optional[int] = None, out=None, stream=None):
+        """ingot_gpu_checksum_fill: compute the selected checksums and write
+        them into the frames, in place (two bytes per layer, nothing else).
+        `out` (optional, (n, 8) uint8) receives the ingot_csum rows after
+        writing; returns it (None when not given)."""
+        return self._checksum("ingot_gpu_checksum_fill", arena, off, lens, recs, what, stride,
+                              n, out, stream)
 
     def flow_hist(self, arena, off, lens, chain: Chain, hist=None, bins: Optional[int] = None,
                   stride: int = 0, n: Optional[int] = None, key: Optional[bytes] = None,

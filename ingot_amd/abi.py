@@ -10,7 +10,7 @@ import enum
 
 import numpy as np
 
-ABI_VERSION = 3
+ABI_VERSION = 4
 
 
 class ParseError(enum.IntEnum):
@@ -378,6 +378,31 @@ def emit_sets_array(sets) -> np.ndarray:
         a[k]["at"], a[k]["field"], a[k]["source"], a[k]["add"] = e[0], int(e[1]), int(e[2]), add
         a[k]["d_values"] = e[4] if len(e) > 4 and e[4] is not None else 0
     return a
+
+
+class CsumState(enum.IntEnum):
+    """enum ingot_csum_state: what ingot_gpu_checksum_verify / _fill say of a layer."""
+
+    NONE = 0      # nothing to check: record not Ok, no such layer, IPv6 (no header sum)
+    OK = 1
+    BAD = 2
+    ZERO = 3      # UDP only: the field is 0, the sender computed none
+    SHORT = 4     # the L3 header's length ends past the frame or inside the L4 header
+    FRAGMENT = 5  # the packet is a fragment; not summed
+
+
+CSUM_L3 = 1
+CSUM_L4 = 2
+
+
+class IngotCsum(ctypes.Structure):
+    _fields_ = [("l3_state", U8), ("l4_state", U8), ("l3_sum", U16), ("l4_sum", U16),
+                ("l4_len", U16)]
+
+
+assert ctypes.sizeof(IngotCsum) == 8
+CSUM_DTYPE = np.dtype(IngotCsum)
+CSUM_BYTES = CSUM_DTYPE.itemsize
 
 
 class GenProfile(enum.IntEnum):

@@ -726,6 +726,48 @@ int ingot_gpu_emit_headers(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_
     return from_hip(ingot_gpu::launch_emit(a, (hipStream_t)stream));
 }
 
+}  // extern "C"
+
+namespace {
+
+// Both checksum calls: every argument is checked before any device work.
+int checksum(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off, const uint16_t* d_len,
+             uint32_t stride, uint64_t n, const ingot_rec* d_rec, uint32_t what,
+             ingot_csum* d_out, bool fill, void* stream) {
+    if (!ctx || what == 0 || (what & ~(INGOT_CSUM_L3 | INGOT_CSUM_L4))) return INGOT_GPU_EINVAL;
+    if (n == 0) return INGOT_GPU_SUCCESS;
+    if (!d_arena || !d_rec || (!d_out && !fill)) return INGOT_GPU_EINVAL;
+    if (!d_off) {
+        if (int e = stride_ok(d_arena, stride)) return e;
+    } else if (!d_len) {
+        return INGOT_GPU_EINVAL;
+    }
+    if (int e = enter(ctx)) return e;
+    ingot_gpu::CsumArgs a{d_arena, d_off, d_len, d_off ? 0u : stride, what, n, d_rec, d_out,
+                          fill ? 1u : 0u};
+    return from_hip(ingot_gpu::launch_csum(a, (hipStream_t)stream));
+}
+
+}  // namespace
+
+extern "C" {
+
+int ingot_gpu_checksum_verify(ingot_gpu_ctx* ctx, const uint8_t* d_arena, const uint64_t* d_off,
+                              const uint16_t* d_len, uint32_t stride, uint64_t n,
+                              const ingot_rec* d_rec, uint32_t what, ingot_csum* d_out,
+                              void* stream) {
+    // the kernel writes the arena only in fill mode
+    return checksum(ctx, const_cast<uint8_t*>(d_arena), d_off, d_len, stride, n, d_rec, what,
+                    d_out, false, stream);
+}
+
+int ingot_gpu_checksum_fill(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off,
+                            const uint16_t* d_len, uint32_t stride, uint64_t n,
+                            const ingot_rec* d_rec, uint32_t what, ingot_csum* d_out,
+                            void* stream) {
+    return checksum(ctx, d_arena, d_off, d_len, stride, n, d_rec, what, d_out, true, stream);
+}
+
 int ingot_gpu_flow_hist_ws(ingot_gpu_ctx* ctx, const uint8_t* d_arena, const uint64_t* d_off,
                            const uint16_t* d_len, uint32_t stride, uint64_t n, int chain,
                            const uint8_t* key, uint32_t bins, uint32_t* d_flow, uint32_t* d_hash,

@@ -1,7 +1,7 @@
 // kernels.h — internal interface between the C ABI (api.cpp) and the HIP
 // kernels: the argument blocks, the tuning record and the launchers of
 // parse.hip, read.hip, ring.hip, tuple.hip, packed.hip, flow.hip, header.hip,
-// emit.hip and stream.hip.  Not part of the public ABI.
+// emit.hip, csum.hip and stream.hip.  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -157,6 +157,20 @@ static_assert(sizeof(EmitArgs) <= 4096, "EmitArgs exceeds the 4 KiB kernel-argum
 // bytes of dynamic LDS one emit block needs (checked against the device)
 size_t emit_lds_bytes(const EmitArgs& a);
 hipError_t launch_emit(const EmitArgs& a, hipStream_t s);
+
+// Batched Internet checksums (ingot_gpu_checksum_verify / _fill, csum.hip).
+struct CsumArgs {
+    uint8_t* arena;        // written only when `fill`
+    const uint64_t* off;   // NULL: slots of `stride`
+    const uint16_t* len;   // NULL (slots only): `stride`
+    uint32_t stride;
+    uint32_t what;         // INGOT_CSUM_L3 | INGOT_CSUM_L4
+    uint64_t n;
+    const ingot_rec* rec;
+    ingot_csum* out;       // optional when `fill`
+    uint32_t fill;
+};
+hipError_t launch_csum(const CsumArgs& a, hipStream_t s);
 
 // Lengths-only packed frames (packed.hip): tile base = u64 base of its group
 // of PACKED_GROUP tiles (at the start of `work`, >= packed_workspace(n)

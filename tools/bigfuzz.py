@@ -6,9 +6,11 @@ defect path), in the packed layout and in 256-B slots; flow ids and hashes
 for the VLAN chain.  Prints one JSON line with the mismatch counts (all must
 be 0) and writes it to gpurun_out/bigfuzz.json.  Also parse_read over random
 4-chunk splits (every staging plan kept, parse_read_first, lazy bounds),
-flow bins from k_flows_bits and from k_parse's flows mode, and the slot ring.
+flow bins from k_flows_bits and from k_parse's flows mode, the slot ring, and
+the checksum calls (`csum`: verify, then fill + verify, against the Python
+model of tests/csum_model.py, so on at most --csum-frames frames per case).
 
-    python tools/bigfuzz.py [--frames 4000000] [--seed 1234]
+    python tools/bigfuzz.py [--frames 4000000] [--seed 1234] [--only csum]
 """
 from __future__ import annotations
 
@@ -24,11 +26,77 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 
 
+def csum_cases(ctx, n, seed, res):
+    """ingot_gpu_checksum_verify on generator frames (random checksums: BAD,
+    SHORT, FRAGMENT, NONE rows), then _fill and a second verify (OK rows), each
+    against the model; packed frames of every chain's profile and 256-B slots."""
+    import torch
+
+    import ingot_amd
+    from ingot_amd import CSUM_DTYPE, Chain, GenProfile
+    from tests import csum_model as model
+
+    def rows(t):
+        return t.cpu().numpy().view(CSUM_DTYPE).reshape(-1)
+
+    cases = [(GenProfile.MIXED, Chain.UdpParser, None),
+             (GenProfile.ADVERSARIAL, Chain.GenericUlp, None),
+             (GenProfile.VLAN_V6EH, Chain.VlanUlp, None), (GenProfile.FLOWS, Chain.VlanUlp, 256),
+             (GenProfile.GENEVE, Chain.GeneveOverV6Tunnel, None),
+             (GenProfile.GENEVE_ADVERSARIAL, Chain.GeneveOverV6Tunnel, None)]
+    for k, (prof, chain, stride) in enumerate(cases):
+        arena, off, lens = ingot_amd.gen_frames(prof, n, seed=seed + 70 + k, stride=stride)
+        st = stride or 0
+        recs = (ctx.parse_strided(arena, stride, n, chain, lens=lens) if stride
+                else ctx.parse(arena, off, lens, chain))
+        got_v = rows(ctx.checksum_verify(arena, off, lens, recs, stride=st, n=n))
+        a = arena.cpu().numpy().copy()
+        o = None if off is None else off.cpu().numpy().view(np.uint64)
+        ln = None if lens is None else lens.cpu().numpy()
+        rec = ingot_amd.records_to_numpy(recs)
+        want_v = model.verify(a, o, ln, rec, 3, st, n)
+        out = torch.zeros((n, 8), dtype=torch.uint8, device="cuda")
+        ctx.checksum_fill(arena, off, lens, recs, stride=st, n=n, out=out)
+        want_f = model.fill(a, o, ln, rec, 3, st, n)
+        got_a = rows(ctx.checksum_verify(arena, off, lens, recs, stride=st, n=n))
+        torch.cuda.synchronize()
+        key = f"csum/{prof.name}/{chain.name}" + (f"/slots{stride}" if stride else "")
+        res[key] = {
+            "verify_row_mismatches": int((got_v.view(np.uint64) != want_v.view(np.uint64)).sum()),
+            "fill_row_mismatches": int((rows(out).view(np.uint64) != want_f.view(np.uint64)).sum()),
+            "fill_byte_mismatches": int((arena.cpu().numpy() != a).sum()),
+            "verify_after_fill_row_mismatches": int((got_a.view(np.uint64)
+                                                     != want_f.view(np.uint64)).sum()),
+            "l4_states_before": np.bincount(want_v["l4_state"], minlength=6).tolist(),
+            "l4_states_after": np.bincount(want_f["l4_state"], minlength=6).tolist()}
+        print(key, res[key], flush=True)
+        del arena, off, lens, recs, out
+        torch.cuda.empty_cache()
+
+
+def finish(n, seed, t0, res):
+    out = {"frames_per_case": n, "seed": seed, "wall_s": round(time.time() - t0, 1),
+           "cases": res,
+           "all_zero": all(v == 0 for c in res.values() for k, v in c.items() if "mismatch" in k)}
+    print(json.dumps(out))
+    (ROOT / "gpurun_out").mkdir(exist_ok=True)
+    (ROOT / "gpurun_out" / "bigfuzz.json").write_text(json.dumps(out, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=4_000_000)
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--csum-frames", type=int, default=200_000,
+                    help="frames per csum case (its reference is a Python model)")
+    ap.add_argument("--only", default="", help="'csum': run only the checksum cases")
     args = ap.parse_args()
+    if args.only == "csum":
+        import ingot_amd
+
+        res, t0 = {}, time.time()
+        csum_cases(ingot_amd.Context(0), min(args.frames, args.csum_frames), args.seed, res)
+        return finish(min(args.frames, args.csum_frames), args.seed, t0, res)
 
     import torch
 
@@ -266,12 +334,8 @@ def main():
         print(key, res[key], flush=True)
         del arena, off, lens, dst, hdst
         torch.cuda.empty_cache()
-    out = {"frames_per_case": n, "seed": args.seed, "wall_s": round(time.time() - t0, 1),
-           "cases": res,
-           "all_zero": all(v == 0 for c in res.values() for k, v in c.items() if "mismatch" in k)}
-    print(json.dumps(out))
-    (ROOT / "gpurun_out").mkdir(exist_ok=True)
-    (ROOT / "gpurun_out" / "bigfuzz.json").write_text(json.dumps(out, indent=1))
+    csum_cases(ctx, min(n, args.csum_frames), args.seed, res)
+    finish(n, args.seed, t0, res)
 
 
 if __name__ == "__main__":
