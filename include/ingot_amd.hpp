@@ -528,6 +528,9 @@ inline std::vector<ReadResult> parse_read_batch(Context& ctx, const std::vector<
 // bitfield set paths, bitfield.rs:188-315), batched: every frame is parsed as
 // `chain` and, when Ok, the edit list is applied in order in place
 // (ingot_gpu_parse_modify).  Returns the rewritten frames and their records.
+// what != 0 (INGOT_CSUM_L3 | INGOT_CSUM_L4 | INGOT_CSUM_OUTER_L4): the same
+// launch also updates those checksums incrementally
+// (ingot_gpu_parse_modify_csum).
 inline ingot_edit edit(uint8_t layer, int field, int op, uint32_t value, uint8_t index = 0) {
     ingot_edit e;
     e.layer = layer;
@@ -545,7 +548,8 @@ struct Modified {
 
 inline std::vector<Modified> modify_batch(Context& ctx,
                                           const std::vector<std::vector<uint8_t>>& frames,
-                                          int chain, const std::vector<ingot_edit>& edits) {
+                                          int chain, const std::vector<ingot_edit>& edits,
+                                          uint32_t what = 0) {
     const size_t n = frames.size();
     std::vector<uint64_t> off(n);
     std::vector<uint16_t> len(n);
@@ -570,9 +574,15 @@ inline std::vector<Modified> modify_batch(Context& ctx,
     hip_check(hipMemcpy(d_arena, arena.data(), arena.size(), hipMemcpyHostToDevice), "H2D");
     hip_check(hipMemcpy(d_off, off.data(), n * 8, hipMemcpyHostToDevice), "H2D");
     hip_check(hipMemcpy(d_len, len.data(), n * 2, hipMemcpyHostToDevice), "H2D");
-    check(ingot_gpu_parse_modify(ctx.get(), d_arena, d_off, d_len, 0, n, chain, edits.data(),
-                                 (uint32_t)edits.size(), d_rec, nullptr),
-          "ingot_gpu_parse_modify");
+    if (what)
+        check(ingot_gpu_parse_modify_csum(ctx.get(), d_arena, d_off, d_len, 0, n, chain,
+                                          edits.data(), (uint32_t)edits.size(), what, d_rec,
+                                          nullptr),
+              "ingot_gpu_parse_modify_csum");
+    else
+        check(ingot_gpu_parse_modify(ctx.get(), d_arena, d_off, d_len, 0, n, chain, edits.data(),
+                                     (uint32_t)edits.size(), d_rec, nullptr),
+              "ingot_gpu_parse_modify");
     std::vector<ingot_rec> rec(n);
     hip_check(hipMemcpy(arena.data(), d_arena, arena.size(), hipMemcpyDeviceToHost), "D2H");
     hip_check(hipMemcpy(rec.data(), d_rec, n * sizeof(ingot_rec), hipMemcpyDeviceToHost), "D2H");

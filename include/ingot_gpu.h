@@ -38,7 +38,8 @@
 extern "C" {
 #endif
 
-/* 4: ingot_gpu_checksum_verify / ingot_gpu_checksum_fill (ingot_csum).
+/* 4: ingot_gpu_checksum_verify / ingot_gpu_checksum_fill (ingot_csum);
+ *    ingot_gpu_parse_modify_csum (an added call: the number stays).
  * 3: ingot_gpu_comm_wrap (borrow the host's RCCL communicator).
  * 2: ingot_gpu_comm_* / ingot_gpu_flow_hist_allreduce (config 5's reduce);
  *    host mappings counted per map, ingot_gpu_host_unmap EINVAL for a pointer
@@ -949,6 +950,56 @@ int ingot_gpu_checksum_fill(ingot_gpu_ctx* ctx, uint8_t* d_arena,
                             const uint64_t* d_off, const uint16_t* d_len,
                             uint32_t stride, uint64_t n, const ingot_rec* d_rec,
                             uint32_t what, ingot_csum* d_out, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Parse + rewrite + incremental checksum update (RFC 1624) in one launch: what
+ * a forwarding caller does after decrementing a hop limit or translating an
+ * address or a port (OPTE updates its sums this way per packet on the CPU).
+ * Frames, edits, records and argument checks are exactly those of
+ * ingot_gpu_parse_modify.  After the edits of a packet that parsed Ok, the
+ * checksums selected by `what` (INGOT_CSUM_L3 | INGOT_CSUM_L4 |
+ * INGOT_CSUM_OUTER_L4) are updated from the bytes the edits changed — no
+ * payload byte is read.  Build-defined, like ingot_csum;
+ * tests/csum_update_model.py is the definition.
+ *
+ * Words are the big-endian 16-bit words at even frame offsets (every header
+ * of every chain starts at an even frame offset).  For a sum whose field holds
+ * HC after the edits, D = the sum of (~m + m') mod 0xffff over its covered
+ * words, m the word before the call and m' the word after the edits.
+ * D == 0 (mod 0xffff): the field is not written (a sum that does not move
+ * keeps its representation, also 0xffff).  Otherwise x = (~HC + D) mod 0xffff
+ * taken in [1, 0xffff] and HC' = ~x (RFC 1624 eqn. 3).
+ *   L3        IPv4 only; covered: the header except its checksum field (at
+ *             l3_off + 10).
+ *   L4        when l4_kind is TCP, UDP, ICMPv4 or ICMPv6; field at l4_off + 16
+ *             (TCP), + 6 (UDP), + 2 (ICMP).  Covered: the fixed L4 header (TCP
+ *             20 B, UDP 8 B, ICMP its first 4 B) except the field, and, where
+ *             ingot_gpu_checksum_fill sums an IPv4 pseudo-header (not ICMPv4),
+ *             the IPv4 source and destination.  Skipped when the IPv4
+ *             fragment offset is non-zero after the edits (those bytes are no
+ *             L4 header); a first fragment (MF set, offset 0) is updated.
+ *             UDP: a field that is 0 after the edits stays 0, and a result of
+ *             0 is written as 0xffff.
+ *   OUTER_L4  GENEVE_OVER_V6 only (any other chain: EINVAL): outer_udp's
+ *             checksum, at its offset + 6.  Covered: every byte from outer_udp
+ *             to the frame's end except that field — the Geneve fields, the
+ *             inner headers and the inner checksum fields this same call
+ *             rewrote (the inner sums are updated first).  The UDP rules apply.
+ * An edit whose target is a checksum field itself is applied as written and
+ * is left out of that sum's D.  A frame whose sum was wrong stays wrong by the
+ * same amount.
+ *
+ * EINVAL besides ingot_gpu_parse_modify's: what == 0 or any bit above 7, and
+ * an edit list that names V4_IHL, V4_TOTAL_LEN, V4_PROTOCOL, V6_PAYLOAD_LEN or
+ * V6_NEXT_HEADER: they move a sum's extent or its pseudo-header, so no
+ * incremental update exists — rewrite, then ingot_gpu_checksum_fill.
+ * ------------------------------------------------------------------------- */
+#define INGOT_CSUM_OUTER_L4 4u   /* GENEVE_OVER_V6 only: outer_udp's checksum */
+int ingot_gpu_parse_modify_csum(ingot_gpu_ctx* ctx, uint8_t* d_arena,
+                                const uint64_t* d_off, const uint16_t* d_len,
+                                uint32_t stride, uint64_t n, int chain,
+                                const ingot_edit* edits, uint32_t n_edits,
+                                uint32_t what, ingot_rec* d_out, void* stream);
 
 /*
  * Flow classification + per-flow histogram (config 5; build-defined, ingot

@@ -27,6 +27,7 @@ from .abi import (  # noqa: F401  (re-exports)
     CSUM_DTYPE,
     CSUM_L3,
     CSUM_L4,
+    CSUM_OUTER_L4,
     CsumState,
     IngotCsum,
     FIELDS_BYTES,
@@ -65,7 +66,8 @@ __all__ = [
     "Chain", "Context", "GenProfile", "PacketParseError", "ParseError", "UdpParser",
     "GenericUlp", "VlanUlp", "GeneveOverV6Tunnel", "gen_frames", "gen_lengths", "records_to_numpy",
     "fields_to_numpy", "load_library", "Parsed", "chunk_tables", "HeaderKind", "parse_header",
-    "HeaderParseError", "first_chunks", "CsumState", "CSUM_L3", "CSUM_L4", "CSUM_DTYPE",
+    "HeaderParseError", "first_chunks", "CsumState", "CSUM_L3", "CSUM_L4", "CSUM_OUTER_L4",
+    "CSUM_DTYPE",
 ]
 
 
@@ -473,17 +475,27 @@ class Context:
         return out, chunk
 
     def parse_modify(self, arena, off, lens, chain: Chain, edits, stride: int = 0,
-                     n: Optional[int] = None, out=None, stream=None):
+                     n: Optional[int] = None, out=None, stream=None, csum: int = 0):
         """Parse, then rewrite header fields in place (ingot's setters):
         edits = [(layer, Field, EditOp, value[, vlan index]), ...] applied in
         order to packets that parse Ok.  Returns the parse records if `out`
-        (an (n, 16) uint8 tensor) is given, else None."""
+        (an (n, 16) uint8 tensor) is given, else None.
+
+        csum != 0 (CSUM_L3 | CSUM_L4 | CSUM_OUTER_L4): the same launch also
+        updates those checksums from the bytes the edits changed (RFC 1624,
+        ingot_gpu_parse_modify_csum)."""
         if n is None:
             n = off.numel()
         self._frames(arena, off, lens, stride, n)
         self._arg("out", out, _U8, n * REC_BYTES, optional=True)
         e = edits_array(edits)
         self._on_device(arena=arena, off=off, lens=lens, out=out)
+        if int(csum):
+            _lib.check(self._lib.ingot_gpu_parse_modify_csum(
+                self._h, _ptr(arena), _ptr(off), _ptr(lens), int(stride), n, int(chain),
+                e.ctypes.data_as(ctypes.c_void_p), len(e), int(csum), _ptr(out),
+                _stream(stream, self.device)), "ingot_gpu_parse_modify_csum")
+            return out
         _lib.check(self._lib.ingot_gpu_parse_modify(
             self._h, _ptr(arena), _ptr(off), _ptr(lens), int(stride), n, int(chain),
             e.ctypes.data_as(ctypes.c_void_p), len(e), _ptr(out), _stream(stream, self.device)),

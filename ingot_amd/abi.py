@@ -393,6 +393,7 @@ class CsumState(enum.IntEnum):
 
 CSUM_L3 = 1
 CSUM_L4 = 2
+CSUM_OUTER_L4 = 4  # ingot_gpu_parse_modify_csum on the tunnel chain: outer_udp's checksum
 
 
 class IngotCsum(ctypes.Structure):

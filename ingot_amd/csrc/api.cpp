@@ -603,13 +603,52 @@ int ingot_gpu_parse_read_dense(ingot_gpu_ctx* ctx, const uint8_t* d_arena, const
                                             tuning_for(ctx, d_arena), (hipStream_t)stream));
 }
 
-int ingot_gpu_parse_modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off,
-                           const uint16_t* d_len, uint32_t stride, uint64_t n, int chain,
-                           const ingot_edit* edits, uint32_t n_edits, ingot_rec* d_out,
-                           void* stream) {
+}  // extern "C"
+
+namespace {
+
+// Which sums the bytes of an edit of `field` at chain layer `layer` are covered
+// by (ingot_gpu_parse_modify_csum), limited to the sums `what` selects; -1 for
+// a field that moves a sum's extent or its pseudo-header's length or protocol.
+// A checksum field is left out of its own sum; the tunnel's outer UDP sum
+// covers everything from outer_udp (layer 2) on except its own field.
+int csum_feeds(int chain, const ingot_edit& e, uint32_t what) {
+    using namespace ingot_gpu;
+    switch (e.field) {
+    case INGOT_F_V4_IHL: case INGOT_F_V4_TOTAL_LEN: case INGOT_F_V4_PROTOCOL:
+    case INGOT_F_V6_PAYLOAD_LEN: case INGOT_F_V6_NEXT_HEADER:
+        return -1;
+    default: break;
+    }
+    const bool tun = chain == INGOT_CHAIN_GENEVE_OVER_V6;
+    const uint8_t kind = kFieldGeo[e.field].kind;
+    uint32_t f = 0;
+    // (the tunnel's layer 2 is the outer UDP header, not the parsed L4 layer)
+    const bool l4_layer = !tun || e.layer == 6;
+    if (kind == HK_V4 && e.field != INGOT_F_V4_CHECKSUM && (what & INGOT_CSUM_L3)) f |= FEED_L3;
+    if ((e.field == INGOT_F_V4_SOURCE || e.field == INGOT_F_V4_DESTINATION) &&
+        (what & INGOT_CSUM_L4))
+        f |= FEED_PSEUDO4;
+    if ((kind == HK_TCP || kind == HK_UDP || kind == HK_ICMP) && l4_layer &&
+        e.field != INGOT_F_TCP_CHECKSUM && e.field != INGOT_F_UDP_CHECKSUM &&
+        e.field != INGOT_F_ICMP_CHECKSUM && (what & INGOT_CSUM_L4))
+        f |= FEED_L4;
+    if (tun && e.layer >= 2 && !(e.layer == 2 && e.field == INGOT_F_UDP_CHECKSUM) &&
+        (what & INGOT_CSUM_OUTER_L4))
+        f |= FEED_OUTER;
+    return (int)f;
+}
+
+// ingot_gpu_parse_modify (what == 0) and ingot_gpu_parse_modify_csum: every
+// argument is checked before any device work.
+int modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off, const uint16_t* d_len,
+           uint32_t stride, uint64_t n, int chain, const ingot_edit* edits, uint32_t n_edits,
+           uint32_t what, ingot_rec* d_out, void* stream) {
     if (!ctx || !chain_ok(chain) || n_edits > INGOT_MAX_EDITS || (n_edits && !edits))
         return INGOT_GPU_EINVAL;
-    ingot_gpu::ModifyArgs a{};
+    ingot_gpu::ModifyCsumArgs c{};  // (the checksum update's extras: used when what != 0)
+    ingot_gpu::ModifyArgs& a = c.m;
+    c.what = what;
     for (uint32_t k = 0; k < n_edits; ++k) {
         const ingot_edit& e = edits[k];
         if (e.field >= INGOT_F_COUNT || e.op > INGOT_OP_XOR ||
@@ -626,6 +665,11 @@ int ingot_gpu_parse_modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t*
         d.rshift = (uint8_t)((8u - ((g.bit + g.bits) % 8u)) % 8u);
         d.bits = g.bits;
         d.value = e.value;
+        if (what) {
+            const int f = csum_feeds(chain, e, what);
+            if (f < 0) return INGOT_GPU_EINVAL;
+            c.feeds[k] = (uint8_t)f;
+        }
     }
     a.n_edits = n_edits;
     if (n == 0) return INGOT_GPU_SUCCESS;
@@ -639,8 +683,33 @@ int ingot_gpu_parse_modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t*
     }
     if (int e = enter(ctx)) return e;
     a.p = ingot_gpu::ParseArgs{d_arena, d_off, d_len, stride, n, d_out};
-    return from_hip(ingot_gpu::launch_modify(a, layout, chain, tuning_for(ctx, d_arena),
-                                             (hipStream_t)stream));
+    const ingot_gpu::Tuning t = tuning_for(ctx, d_arena);
+    return from_hip(what ? ingot_gpu::launch_modify_csum(c, layout, chain, t, (hipStream_t)stream)
+                         : ingot_gpu::launch_modify(a, layout, chain, t, (hipStream_t)stream));
+}
+
+}  // namespace
+
+extern "C" {
+
+int ingot_gpu_parse_modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off,
+                           const uint16_t* d_len, uint32_t stride, uint64_t n, int chain,
+                           const ingot_edit* edits, uint32_t n_edits, ingot_rec* d_out,
+                           void* stream) {
+    return modify(ctx, d_arena, d_off, d_len, stride, n, chain, edits, n_edits, 0u, d_out,
+                  stream);
+}
+
+int ingot_gpu_parse_modify_csum(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off,
+                                const uint16_t* d_len, uint32_t stride, uint64_t n, int chain,
+                                const ingot_edit* edits, uint32_t n_edits, uint32_t what,
+                                ingot_rec* d_out, void* stream) {
+    const uint32_t all = INGOT_CSUM_L3 | INGOT_CSUM_L4 | INGOT_CSUM_OUTER_L4;
+    if (what == 0 || (what & ~all) ||
+        ((what & INGOT_CSUM_OUTER_L4) && chain != INGOT_CHAIN_GENEVE_OVER_V6))
+        return INGOT_GPU_EINVAL;
+    return modify(ctx, d_arena, d_off, d_len, stride, n, chain, edits, n_edits, what, d_out,
+                  stream);
 }
 
 }  // extern "C"

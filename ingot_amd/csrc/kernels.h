@@ -82,6 +82,19 @@ struct ModifyArgs {
     uint32_t n_edits;
     Edit e[INGOT_MAX_EDITS];
 };
+// ingot_gpu_parse_modify_csum: the rewrite's arguments and, after them (so
+// the plain rewrite kernels keep their own argument block, byte for byte),
+// which sums edit k's bytes feed, resolved by api.cpp from the edit's layer
+// and field, and the sums the call selected.
+struct ModifyCsumArgs {
+    ModifyArgs m;
+    uint8_t feeds[INGOT_MAX_EDITS];  // CsumFeed bits
+    uint32_t what;                   // INGOT_CSUM_* bits
+};
+// An edit's bytes are covered by the IPv4 header sum, by its layer's L4 sum
+// (the fixed L4 header), by the L4 sum's IPv4 pseudo-header (the addresses:
+// fed only when the packet's L4 layer has one) or by the tunnel's outer UDP sum.
+enum CsumFeed : uint8_t { FEED_L3 = 1, FEED_L4 = 2, FEED_OUTER = 4, FEED_PSEUDO4 = 8 };
 // 3,824 B today (ParseArgs + key windows + the 16-bit table): the kernarg
 // segment is 4 KiB, and a larger FlowArgs would fail flow launches at run
 // time, not here.
@@ -227,6 +240,11 @@ hipError_t launch_slot_ring(const ParseArgs& a, int chain, int mode, const Tunin
 hipError_t launch_modify_ring(const ModifyArgs& a, int chain, const Tuning& t, hipStream_t s);
 hipError_t launch_modify(const ModifyArgs& a, int layout_kind, int chain, const Tuning& t,
                          hipStream_t s);
+// The same two with the fused checksum update (the CSUM instantiations).
+hipError_t launch_modify_ring_csum(const ModifyCsumArgs& a, int chain, const Tuning& t,
+                                   hipStream_t s);
+hipError_t launch_modify_csum(const ModifyCsumArgs& a, int layout_kind, int chain,
+                              const Tuning& t, hipStream_t s);
 bool tuning_valid(int key, int value);
 
 }  // namespace ingot_gpu

@@ -32,8 +32,12 @@
 namespace ingot_gpu {
 namespace {
 
+// ARGS = ModifyCsumArgs (OUT_MODIFY only): the fused checksum update after the
+// edits (ingot_gpu_parse_modify_csum; walk.h: csum_finish).
 template <uint32_t NCH, int LAYOUT, int CHAIN, int MODE, class ARGS>
 __global__ __launch_bounds__(BLOCK) void k_parse(ARGS args) {
+    constexpr bool CSUM = std::is_same<ARGS, ModifyCsumArgs>::value;
+    static_assert(!CSUM || MODE == OUT_MODIFY, "checksums are updated by the rewrite only");
     const ParseArgs& a = base_args(args);
     constexpr bool TUN = CHAIN == INGOT_CHAIN_GENEVE_OVER_V6;
     constexpr uint32_t WIN = NCH * 16u;
@@ -178,12 +182,23 @@ __global__ __launch_bounds__(BLOCK) void k_parse(ARGS args) {
             if (valid && r.status == INGOT_OK) {
                 EditSink sink{const_cast<uint8_t*>(a.arena) + off, off, base, len, NCH ? nch : 0u,
                               0u, mis};
-                for (uint32_t k = 0; k < args.n_edits; ++k) {
-                    const Edit e = args.e[k];
+                [[maybe_unused]] typename std::conditional<CSUM, CsumAcc, NoCsum>::type acc;
+                const ModifyArgs& m = edit_args(args);
+                for (uint32_t k = 0; k < m.n_edits; ++k) {
+                    const Edit e = m.e[k];
                     uint32_t h;
-                    if (header_at<CHAIN>(r, e.layer, e.kind, e.index, h))
-                        apply_edit(fr, sink, h, e);
+                    if (header_at<CHAIN>(r, e.layer, e.kind, e.index, h)) {
+                        if constexpr (CSUM)
+                            csum_feed(acc, args.feeds[k], r, apply_edit<true>(fr, sink, h, e));
+                        else
+                            apply_edit(fr, sink, h, e);
+                    }
                 }
+                // the two checksum bytes go through the edits' sink, so the
+                // write-back sectors stay whole
+                if constexpr (CSUM)
+                    csum_finish<CHAIN>(fr, r, args.what, acc,
+                                       [&](uint32_t at, uint8_t v) { put_byte(fr, sink, at, v); });
                 // whole-sector write-back of the staged copy
                 uint4* dst = reinterpret_cast<uint4*>(const_cast<uint8_t*>(a.arena) + base);
                 for (uint32_t d = sink.dirty; d; d &= d - 1u) {
@@ -340,26 +355,42 @@ hipError_t launch_parse(const ParseArgs& args, int layout_kind, int chain, int m
     }
 }
 
-// Parse + rewrite: the default windows of the record path.
-hipError_t launch_modify(const ModifyArgs& args, int layout_kind, int chain, const Tuning& t,
-                         hipStream_t s) {
-    if (args.p.n == 0) return hipSuccess;
-    ModifyArgs a = args;
-    const uint32_t g = grid_for(a.p.n, t.max_blocks);
+// Parse + rewrite: the default windows of the record path.  ARGS = ModifyArgs,
+// or ModifyCsumArgs for the fused checksum update.
+template <class ARGS>
+static hipError_t launch_modify_as(const ARGS& a, int layout_kind, int chain, const Tuning& t,
+                                   hipStream_t s) {
+    const ParseArgs& p = edit_args(a).p;
+    if (p.n == 0) return hipSuccess;
+    const uint32_t g = grid_for(p.n, t.max_blocks);
     const bool tun = chain == INGOT_CHAIN_GENEVE_OVER_V6;
     // Slot rings (slots >= 64 B, no length array): the multi-tile kernel with
     // lane-linear write-back (k_modify_pipe).  Defaults measured on MI355X
     // (DESIGN.md §1c): write-back unit WB, plain staging loads.
-    if (t.pipeline != 1 && !t.window_strided && layout_kind == LAYOUT_STRIDED && !a.p.len &&
-        !tun && a.p.stride >= 64u)
-        return launch_modify_ring(a, chain, t, s);
+    if (t.pipeline != 1 && !t.window_strided && layout_kind == LAYOUT_STRIDED && !p.len && !tun &&
+        p.stride >= 64u) {
+        if constexpr (std::is_same<ARGS, ModifyCsumArgs>::value)
+            return launch_modify_ring_csum(a, chain, t, s);
+        else
+            return launch_modify_ring(a, chain, t, s);
+    }
     if (layout_kind == LAYOUT_STRIDED) {
         if (tun) return launch_chain<8, LAYOUT_STRIDED, OUT_MODIFY>(a, chain, g, s);
-        return a.p.stride <= 64u ? launch_chain<4, LAYOUT_STRIDED, OUT_MODIFY>(a, chain, g, s)
-                                 : launch_chain<3, LAYOUT_STRIDED, OUT_MODIFY>(a, chain, g, s);
+        return p.stride <= 64u ? launch_chain<4, LAYOUT_STRIDED, OUT_MODIFY>(a, chain, g, s)
+                               : launch_chain<3, LAYOUT_STRIDED, OUT_MODIFY>(a, chain, g, s);
     }
     return tun ? launch_chain<8, LAYOUT_INDEXED, OUT_MODIFY>(a, chain, g, s)
                : launch_chain<3, LAYOUT_INDEXED, OUT_MODIFY>(a, chain, g, s);
+}
+
+hipError_t launch_modify(const ModifyArgs& a, int layout_kind, int chain, const Tuning& t,
+                         hipStream_t s) {
+    return launch_modify_as(a, layout_kind, chain, t, s);
+}
+
+hipError_t launch_modify_csum(const ModifyCsumArgs& a, int layout_kind, int chain,
+                              const Tuning& t, hipStream_t s) {
+    return launch_modify_as(a, layout_kind, chain, t, s);
 }
 
 // Flow mode needs the addresses (IPv6: 32 bytes past byte 22) and ports, so

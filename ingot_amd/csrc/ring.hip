@@ -398,8 +398,14 @@ __global__ __launch_bounds__(BLOCK) void k_parse_ring(RingArgs a) {
 // staging map, so one store instruction covers 16 consecutive slots instead
 // of 64 scattered ones.  Write-back unit `a.wb` bytes (16, 32 or 64, aligned
 // within the slot); slots >= 64 B, the whole window inside every frame.
-template <uint32_t NCH, uint32_t DEPTH, int CHAIN>
-__global__ __launch_bounds__(BLOCK) void k_modify_pipe(ModifyArgs m) {
+// ARGS = ModifyCsumArgs (ingot_gpu_parse_modify_csum): each applied edit's
+// RFC 1624 term goes into the lane's accumulators, and after the edits the
+// checksum fields are updated through the same staged-copy / dirty-unit /
+// direct-store paths (walk.h: csum_finish) — no further LDS, no cross-lane work.
+template <uint32_t NCH, uint32_t DEPTH, int CHAIN, class ARGS = ModifyArgs>
+__global__ __launch_bounds__(BLOCK) void k_modify_pipe(ARGS args) {
+    constexpr bool CSUM = std::is_same<ARGS, ModifyCsumArgs>::value;
+    const ModifyArgs& m = edit_args(args);
     const ParseArgs& a = m.p;
     using Img = RingImg<NCH, DEPTH>;
     __shared__ __attribute__((aligned(16))) uint32_t s_img[Img::DW];
@@ -432,6 +438,8 @@ __global__ __launch_bounds__(BLOCK) void k_modify_pipe(ModifyArgs m) {
         walk<CHAIN, false>(fr, r, nullptr, nullptr);
         uint32_t dirty = 0;
         if (valid && r.status == INGOT_OK) {
+            // (no accumulators in the plain kernel, whose code stays as it was)
+            [[maybe_unused]] typename std::conditional<CSUM, CsumAcc, NoCsum>::type acc;
             for (uint32_t k = 0; k < m.n_edits; ++k) {
                 const Edit& e = m.e[k];
                 uint32_t h;
@@ -439,6 +447,7 @@ __global__ __launch_bounds__(BLOCK) void k_modify_pipe(ModifyArgs m) {
                 // the setter (bitfield.rs:188-315): read-modify-write of the
                 // covering bytes through the staged copy
                 uint64_t w = fr.be(h + e.byte0, e.nbytes);
+                [[maybe_unused]] const uint32_t w_old = CSUM ? (uint32_t)w : 0u;
                 const uint32_t fm = e.bits >= 32 ? 0xffffffffu : ((1u << e.bits) - 1u);
                 const uint32_t cur = (uint32_t)(w >> e.rshift) & fm;
                 uint32_t v;
@@ -462,7 +471,20 @@ __global__ __launch_bounds__(BLOCK) void k_modify_pipe(ModifyArgs m) {
                         frame[at] = x;  // past the window (slots > 64 B)
                     }
                 }
+                if constexpr (CSUM)
+                    csum_feed(acc, args.feeds[k], r,
+                              csum_term(h + e.byte0, e.nbytes, w_old, (uint32_t)w));
             }
+            if constexpr (CSUM)
+                csum_finish<CHAIN>(fr, r, args.what, acc, [&](uint32_t at, uint8_t x) {
+                    if (at < Img::WIN) {
+                        fr.put_staged(at, x);
+                        const uint32_t c0 = (at >> 4) & ~(unit_ch - 1u);
+                        dirty |= ((1u << unit_ch) - 1u) << c0;
+                    } else {
+                        frame[at] = x;
+                    }
+                });
         }
         if (valid && a.out) store_rec(static_cast<uint4*>(a.out) + i, pack(r), a.policy);
         // every lane's staged edits are in LDS before any lane reads them back
@@ -519,11 +541,11 @@ hipError_t launch_for_chain(int chain, F&& f) {
     return with_chain(chain, f) ? hipGetLastError() : hipErrorInvalidValue;
 }
 
-template <uint32_t DEPTH>
-hipError_t launch_modify_pipe(const ModifyArgs& a, int chain, uint32_t grid, hipStream_t s) {
+template <uint32_t DEPTH, class ARGS>
+hipError_t launch_modify_pipe(const ARGS& a, int chain, uint32_t grid, hipStream_t s) {
     return launch_for_chain(chain, [&](auto c) {
-        hipLaunchKernelGGL((k_modify_pipe<4, DEPTH, decltype(c)::value>), dim3(grid), dim3(BLOCK),
-                           0, s, a);
+        hipLaunchKernelGGL((k_modify_pipe<4, DEPTH, decltype(c)::value, ARGS>), dim3(grid),
+                           dim3(BLOCK), 0, s, a);
     });
 }
 
@@ -618,15 +640,26 @@ hipError_t launch_slot_ring(const ParseArgs& args, int chain, int mode, const Tu
 // Slot rings (slots >= 64 B, no length array): the multi-tile kernel with
 // lane-linear write-back (k_modify_pipe).  Defaults measured on MI355X
 // (DESIGN.md §1c): write-back unit WB, plain staging loads.
-hipError_t launch_modify_ring(const ModifyArgs& args, int chain, const Tuning& t,
-                              hipStream_t s) {
-    ModifyArgs a = args;
+template <class ARGS>
+static hipError_t launch_modify_ring_as(const ARGS& args, int chain, const Tuning& t,
+                                        hipStream_t s) {
+    ARGS b = args;
+    ModifyArgs& a = edit_args(b);
     a.p.xcd_remap = xcd_bits(t.xcd_remap, 1u);  // block order only
     a.wb = t.writeback ? (uint32_t)t.writeback : kModifyRingWb;
     a.p.policy = t.cache_policy ? (uint32_t)t.cache_policy & 0x3bu : kModifyRingPolicy;
     const uint32_t pg = ring_blocks((a.p.n + WAVE - 1) / WAVE, t.pipeline, 2, t.cus);
-    return t.pipe_depth == 3 ? launch_modify_pipe<3>(a, chain, pg, s)
-                             : launch_modify_pipe<2>(a, chain, pg, s);
+    return t.pipe_depth == 3 ? launch_modify_pipe<3>(b, chain, pg, s)
+                             : launch_modify_pipe<2>(b, chain, pg, s);
+}
+
+hipError_t launch_modify_ring(const ModifyArgs& a, int chain, const Tuning& t, hipStream_t s) {
+    return launch_modify_ring_as(a, chain, t, s);
+}
+
+hipError_t launch_modify_ring_csum(const ModifyCsumArgs& a, int chain, const Tuning& t,
+                                   hipStream_t s) {
+    return launch_modify_ring_as(a, chain, t, s);
 }
 
 // The ring consumer's grid is persistent: blocks per CU x CUs (default 2,

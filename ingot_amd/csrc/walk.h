@@ -913,6 +913,14 @@ __device__ __forceinline__ void walk(FR& f, Rec& r, ingot_fields* F, ingot_tunne
 __device__ __forceinline__ const ParseArgs& base_args(const ParseArgs& a) { return a; }
 __device__ __forceinline__ const ParseArgs& base_args(const FlowArgs& a) { return a.p; }
 __device__ __forceinline__ const ParseArgs& base_args(const ModifyArgs& a) { return a.p; }
+__device__ __forceinline__ const ParseArgs& base_args(const ModifyCsumArgs& a) { return a.m.p; }
+// the rewrite's edit list, with or without the checksum update's extras
+__host__ __device__ __forceinline__ const ModifyArgs& edit_args(const ModifyArgs& a) { return a; }
+__host__ __device__ __forceinline__ const ModifyArgs& edit_args(const ModifyCsumArgs& a) {
+    return a.m;
+}
+__host__ __device__ __forceinline__ ModifyArgs& edit_args(ModifyArgs& a) { return a; }
+__host__ __device__ __forceinline__ ModifyArgs& edit_args(ModifyCsumArgs& a) { return a.m; }
 
 // The header at chain layer `layer` of a parsed-Ok record, if it is of `kind`.
 template <int CHAIN>
@@ -988,13 +996,100 @@ __device__ __forceinline__ void put_byte(const FR& f, EditSink& k, uint32_t i, u
     }
 }
 
+// ---------------------------------------------------------------------------
+// Fused checksum update (ingot_gpu_parse_modify_csum; RFC 1624 eqn. 3,
+// tests/csum_update_model.py is the definition).  A sum's delta is
+// D = sum of (~m + m') over its covered 16-bit words, modulo 0xffff.
+//
+// Invariant the byte terms rely on: every header of every chain starts at an
+// even frame offset (Ethernet 14, VLAN 4, ihl * 4, extension headers 8 k, UDP
+// 8, Geneve 8 + 4 k), so the words of all three sums are the big-endian words
+// at even FRAME offsets, and a byte's place in its word is its frame offset's
+// parity, whatever the frame's address.
+// ---------------------------------------------------------------------------
+// The term of `nbytes` (<= 4) bytes at frame offset `at` changing from w_old to
+// w_new (big-endian integers): per byte ~(old << s) + (new << s), s = 8 for an
+// even offset, i.e. the word's term with its other byte unchanged.  At most
+// 4 * 0x1fffe; 16 edits and the inner sums' own terms stay far below 2^32.
+__device__ __forceinline__ uint32_t csum_term(uint32_t at, uint32_t nbytes, uint32_t w_old,
+                                              uint32_t w_new) {
+    uint32_t d = 0;
+    for (uint32_t k = 0; k < nbytes; ++k) {
+        const uint32_t sh = 8u * (nbytes - 1u - k);
+        const uint32_t s = ((at + k) & 1u) ? 0u : 8u;
+        d += (0xffffu ^ (((w_old >> sh) & 0xffu) << s)) + (((w_new >> sh) & 0xffu) << s);
+    }
+    return d;
+}
+
+struct CsumAcc {
+    uint32_t l3 = 0, l4 = 0, outer = 0;
+};
+struct NoCsum {};  // in CsumAcc's place where no checksum is updated
+
+// Edit k's term into the sums it feeds: `feeds` are the host's CsumFeed bits,
+// the record adds the run-time condition of the pseudo-header (ICMPv4 has
+// none; the header kinds themselves were matched by header_at).
+__device__ __forceinline__ void csum_feed(CsumAcc& c, uint32_t feeds, const Rec& r, uint32_t d) {
+    if (feeds & FEED_L3) c.l3 += d;
+    const bool pseudo = (feeds & FEED_PSEUDO4) &&
+                        (r.l4_kind == INGOT_L4_TCP || r.l4_kind == INGOT_L4_UDP ||
+                         r.l4_kind == INGOT_L4_ICMPV6);
+    if ((feeds & FEED_L4) || pseudo) c.l4 += d;
+    if (feeds & FEED_OUTER) c.outer += d;
+}
+
+// After a packet's edits: update the selected checksum fields from the
+// accumulated terms.  `f` is the frame view (it sees the staged edits; the
+// field is read byte by byte, so each byte comes from where its last write
+// went), put(at, byte) the kernel's edit sink.  Inner sums first: their
+// fields' own change is covered by the tunnel's outer UDP sum.
+template <int CHAIN, class FR, class PUT>
+__device__ __forceinline__ void csum_finish(const FR& f, const Rec& r, uint32_t what, CsumAcc& c,
+                                            PUT&& put) {
+    constexpr bool TUN = CHAIN == INGOT_CHAIN_GENEVE_OVER_V6;
+    // field at `at`, delta d (!= 0 mod 0xffff): HC' = ~(~HC + D), the sum taken
+    // in [1, 0xffff]; UDP keeps a field of 0 and sends a result of 0 as 0xffff
+    auto update = [&](uint32_t at, uint32_t d, bool udp) {
+        if (d % 0xffffu == 0u) return;  // the sum did not move: representation kept
+        const uint32_t hc = (f.be(at, 1) << 8) | f.be(at + 1u, 1);
+        if (udp && hc == 0u) return;
+        uint32_t x = ((hc ^ 0xffffu) + d) % 0xffffu;
+        if (x == 0u) x = 0xffffu;
+        uint32_t n = x ^ 0xffffu;
+        if (udp && n == 0u) n = 0xffffu;
+        put(at, (uint8_t)(n >> 8));
+        put(at + 1u, (uint8_t)n);
+        if constexpr (TUN) c.outer += (hc ^ 0xffffu) + n;
+    };
+    if ((what & INGOT_CSUM_L3) && r.l3_kind == INGOT_L3_IPV4)
+        update(r.l3_off + ipv4::checksum.byte0(), c.l3, false);
+    if ((what & INGOT_CSUM_L4) && r.l4_kind != INGOT_L4_NONE) {
+        // a non-first IPv4 fragment's bytes at l4_off are not an L4 header
+        const bool later_frag =
+            r.l3_kind == INGOT_L3_IPV4 && f.get(r.l3_off, ipv4::fragment_offset) != 0u;
+        const uint32_t at = r.l4_kind == INGOT_L4_TCP ? 16u : r.l4_kind == INGOT_L4_UDP ? 6u : 2u;
+        if (!later_frag) update(r.l4_off + at, c.l4, r.l4_kind == INGOT_L4_UDP);
+    }
+    if constexpr (TUN) {
+        if (what & INGOT_CSUM_OUTER_L4) {
+            const uint32_t d = c.outer;
+            c.outer = 0;  // (update adds the field's own term: not covered)
+            update(r.o_udp + 6u, d, true);
+        }
+    }
+}
+
 // One generated setter: read-modify-write of the field's covering bytes,
 // neighbouring bits preserved (bitfield.rs:188-315), big-endian.  The bytes
 // are read through the frame view (staged window first).
-template <class FR>
-__device__ __forceinline__ void apply_edit(const FR& f, EditSink& sink, uint32_t h,
-                                           const Edit& e) {
+// CSUM: returns the bytes' RFC 1624 term (csum_term) for the fused checksum
+// update; otherwise 0.
+template <bool CSUM = false, class FR>
+__device__ __forceinline__ uint32_t apply_edit(const FR& f, EditSink& sink, uint32_t h,
+                                               const Edit& e) {
     uint64_t w = f.be(h + e.byte0, e.nbytes);  // fields span <= 4 bytes
+    [[maybe_unused]] const uint32_t w_old = (uint32_t)w;
     const uint32_t fm = e.bits >= 32 ? 0xffffffffu : ((1u << e.bits) - 1u);
     const uint32_t cur = (uint32_t)(w >> e.rshift) & fm;
     uint32_t v;
@@ -1009,6 +1104,8 @@ __device__ __forceinline__ void apply_edit(const FR& f, EditSink& sink, uint32_t
     w = (w & ~((uint64_t)fm << e.rshift)) | ((uint64_t)(v & fm) << e.rshift);
     for (uint32_t k = 0; k < e.nbytes; ++k)
         put_byte(f, sink, h + e.byte0 + k, (uint8_t)(w >> (8u * (e.nbytes - 1u - k))));
+    if constexpr (CSUM) return csum_term(h + e.byte0, e.nbytes, w_old, (uint32_t)w);
+    else return 0u;
 }
 
 // RSS Toeplitz over one 32-bit input word (MSB first) whose first bit is

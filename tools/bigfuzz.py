@@ -8,9 +8,11 @@ be 0) and writes it to gpurun_out/bigfuzz.json.  Also parse_read over random
 4-chunk splits (every staging plan kept, parse_read_first, lazy bounds),
 flow bins from k_flows_bits and from k_parse's flows mode, the slot ring, and
 the checksum calls (`csum`: verify, then fill + verify, against the Python
-model of tests/csum_model.py, so on at most --csum-frames frames per case).
+model of tests/csum_model.py, so on at most --csum-frames frames per case),
+and the rewrite with the fused checksum update (`modify_csum`: against the
+oracle's rewrite + the Python model of tests/csum_update_model.py, same cap).
 
-    python tools/bigfuzz.py [--frames 4000000] [--seed 1234] [--only csum]
+    python tools/bigfuzz.py [--frames 4000000] [--seed 1234] [--only csum|modify_csum]
 """
 from __future__ import annotations
 
@@ -74,6 +76,81 @@ def csum_cases(ctx, n, seed, res):
         torch.cuda.empty_cache()
 
 
+def modify_csum_cases(ctx, n, seed, res):
+    """ingot_gpu_parse_modify_csum against the oracle's rewrite followed by the
+    update model: the checksum cases' profiles x chains x layouts (packed
+    frames, 256-B slots with lengths) and 64- and 128-B slot rings, on the
+    generator's frames as they are (random sums stay wrong by the same
+    amount) and, every other case, with their sums filled first."""
+    import torch
+
+    import ingot_amd
+    import oracle
+    from ingot_amd import CSUM_L3, CSUM_L4, CSUM_OUTER_L4, Chain, EditOp, Field, GenProfile
+    from tests import csum_update_model as upd
+
+    def edits(l3):
+        l4 = l3 + 1
+        return [(l3, Field.V4_HOP_LIMIT, EditOp.SUB, 1), (l3, Field.V4_SOURCE, EditOp.SET, 0x0A000001),
+                (l3, Field.V4_DESTINATION, EditOp.XOR, 0x00FF00FF),
+                (l4, Field.UDP_DESTINATION, EditOp.SUB, 1), (l4, Field.TCP_SOURCE, EditOp.SET, 0),
+                (l4, Field.TCP_FLAGS, EditOp.OR, 0x10), (l3, Field.V4_DSCP, EditOp.SET, 0x2E),
+                (l3, Field.V6_HOP_LIMIT, EditOp.SUB, 1), (l4, Field.ICMP_CODE, EditOp.ADD, 1),
+                (l3, Field.V4_FRAGMENT_OFFSET, EditOp.AND, 0x1F00),
+                (l4, Field.UDP_CHECKSUM, EditOp.XOR, 0x0100), (l4, Field.TCP_SEQUENCE, EditOp.ADD,
+                                                               0x80000001)]
+
+    tun = Chain.GeneveOverV6Tunnel
+    l3_of = {Chain.UdpParser: 1, Chain.GenericUlp: 1, Chain.VlanUlp: 2, tun: 5}
+    cases = [(GenProfile.MIXED, Chain.UdpParser, None, True),
+             (GenProfile.ADVERSARIAL, Chain.GenericUlp, None, True),
+             (GenProfile.VLAN_V6EH, Chain.VlanUlp, None, True),
+             (GenProfile.FLOWS, Chain.VlanUlp, 256, True),
+             (GenProfile.GENEVE, tun, None, True), (GenProfile.GENEVE_ADVERSARIAL, tun, None, True),
+             (GenProfile.V4UDP64, Chain.UdpParser, 64, False),
+             (GenProfile.ADVERSARIAL, Chain.GenericUlp, 64, False),
+             (GenProfile.MIXED, Chain.GenericUlp, 128, False),
+             (GenProfile.VLAN_V6EH, Chain.VlanUlp, 128, False)]
+    for k, (prof, chain, stride, with_lens) in enumerate(cases):
+        arena, off, lens = ingot_amd.gen_frames(prof, n, seed=seed + 90 + k, stride=stride)
+        if not with_lens:
+            lens = None  # whole slots: the ring kernel
+        st = stride or 0
+        if k % 2:
+            recs = (ctx.parse_strided(arena, stride, n, chain, lens=lens) if stride
+                    else ctx.parse(arena, off, lens, chain))
+            ctx.checksum_fill(arena, off, lens, recs, stride=st, n=n)
+            torch.cuda.synchronize()
+        before = arena.cpu().numpy().copy()
+        o = None if off is None else off.cpu().numpy().view(np.uint64)
+        ln = None if lens is None else lens.cpu().numpy()
+        e = edits(l3_of[chain])
+        what = CSUM_L3 | CSUM_L4
+        if chain == tun:
+            what |= CSUM_OUTER_L4
+            e += [(3, Field.GENEVE_VNI, EditOp.ADD, 1), (2, Field.UDP_SOURCE, EditOp.XOR, 0x0FF0)]
+        got_rec = torch.empty((n, 16), dtype=torch.uint8, device="cuda")
+        ctx.parse_modify(arena, off, lens, chain, e, stride=st, n=n, out=got_rec, csum=what)
+        torch.cuda.synchronize()
+        want = before.copy()
+        w_rec = oracle.parse_modify_batch(want, o, ln, chain, e, stride=st, n=n, nthreads=16)
+        o_udp = (oracle.geneve_fields_batch(before, o, ln, stride=st, n=n)["outer"]["outer_udp_off"]
+                 if chain == tun else None)
+        rewritten = want.copy()
+        upd.update(before, want, o, ln, w_rec, what, o_udp=o_udp, stride=st, n=n)
+        key = f"modify_csum/{prof.name}/{chain.name}" + (
+            f"/slots{stride}" + ("" if with_lens else "_ring") if stride else "")
+        res[key] = {
+            "byte_mismatches": int((arena.cpu().numpy() != want).sum()),
+            "record_mismatches": int((got_rec.cpu().numpy().reshape(n, -1) !=
+                                      w_rec.view(np.uint8).reshape(n, -1)).any(axis=1).sum()),
+            "sums_filled_first": bool(k % 2),
+            "checksum_bytes_moved": int((want != rewritten).sum())}
+        print(key, res[key], flush=True)
+        del arena, off, lens, got_rec
+        torch.cuda.empty_cache()
+
+
 def finish(n, seed, t0, res):
     out = {"frames_per_case": n, "seed": seed, "wall_s": round(time.time() - t0, 1),
            "cases": res,
@@ -89,13 +166,15 @@ def main():
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--csum-frames", type=int, default=200_000,
                     help="frames per csum case (its reference is a Python model)")
-    ap.add_argument("--only", default="", help="'csum': run only the checksum cases")
+    ap.add_argument("--only", default="",
+                    help="'csum' / 'modify_csum': run only that case group")
     args = ap.parse_args()
-    if args.only == "csum":
+    if args.only in ("csum", "modify_csum"):
         import ingot_amd
 
         res, t0 = {}, time.time()
-        csum_cases(ingot_amd.Context(0), min(args.frames, args.csum_frames), args.seed, res)
+        group = csum_cases if args.only == "csum" else modify_csum_cases
+        group(ingot_amd.Context(0), min(args.frames, args.csum_frames), args.seed, res)
         return finish(min(args.frames, args.csum_frames), args.seed, t0, res)
 
     import torch
@@ -335,6 +414,7 @@ def main():
         del arena, off, lens, dst, hdst
         torch.cuda.empty_cache()
     csum_cases(ctx, min(n, args.csum_frames), args.seed, res)
+    modify_csum_cases(ctx, min(n, args.csum_frames), args.seed, res)
     finish(n, args.seed, t0, res)
 
 
