@@ -598,7 +598,15 @@ inline std::vector<Modified> modify_batch(Context& ctx,
 // Batched Emit (ingot_gpu_emit_packets): `hdr` = an owned header stack
 // emitted once (ingot's emit_vec on the host), the setters applied per packet
 // (values per packet for INGOT_EMIT_U16 / U32 sources), then each payload.
-// Returns the emitted packets.
+// Returns the emitted packets.  `sums` (optional): the outer checksums to
+// fill in the same launch (ingot_gpu_emit_packets_csum), e.g.
+// {{INGOT_EMIT_SUM_UDP, 54, 14}, {INGOT_EMIT_SUM_IPV4, 14}}; empty = the plain
+// entry point.
+struct EmitSum {
+    int kind;            // enum ingot_emit_sum_kind
+    uint16_t at;         // the header that holds the checksum field
+    uint16_t l3_at = 0;  // UDP: the IPv4 / IPv6 header of the pseudo-header
+};
 struct EmitSet {
     uint16_t at;
     int field;
@@ -609,7 +617,8 @@ struct EmitSet {
 
 inline std::vector<std::vector<uint8_t>> emit_batch(Context& ctx, const std::vector<uint8_t>& hdr,
                                                     const std::vector<EmitSet>& sets,
-                                                    const std::vector<std::vector<uint8_t>>& payloads) {
+                                                    const std::vector<std::vector<uint8_t>>& payloads,
+                                                    const std::vector<EmitSum>& sums = {}) {
     const size_t n = payloads.size();
     std::vector<uint64_t> off(n), doff(n);
     std::vector<uint16_t> len(n);
@@ -656,10 +665,20 @@ inline std::vector<std::vector<uint8_t>> emit_batch(Context& ctx, const std::vec
     hip_check(hipMemcpy(d_off, off.data(), n * 8, hipMemcpyHostToDevice), "H2D");
     hip_check(hipMemcpy(d_doff, doff.data(), n * 8, hipMemcpyHostToDevice), "H2D");
     hip_check(hipMemcpy(d_len, len.data(), n * 2, hipMemcpyHostToDevice), "H2D");
-    check(ingot_gpu_emit_packets(ctx.get(), hdr.data(), (uint32_t)hdr.size(), es.data(),
-                                 (uint32_t)es.size(), d_arena, d_off, d_len, n, d_dst, d_doff,
-                                 nullptr),
-          "ingot_gpu_emit_packets");
+    if (sums.empty()) {
+        check(ingot_gpu_emit_packets(ctx.get(), hdr.data(), (uint32_t)hdr.size(), es.data(),
+                                     (uint32_t)es.size(), d_arena, d_off, d_len, n, d_dst, d_doff,
+                                     nullptr),
+              "ingot_gpu_emit_packets");
+    } else {
+        std::vector<ingot_emit_sum> cs(sums.size());
+        for (size_t k = 0; k < sums.size(); ++k)
+            cs[k] = ingot_emit_sum{sums[k].at, sums[k].l3_at, (uint8_t)sums[k].kind, {0, 0, 0}};
+        check(ingot_gpu_emit_packets_csum(ctx.get(), hdr.data(), (uint32_t)hdr.size(), es.data(),
+                                          (uint32_t)es.size(), cs.data(), (uint32_t)cs.size(),
+                                          d_arena, d_off, d_len, n, d_dst, d_doff, nullptr),
+              "ingot_gpu_emit_packets_csum");
+    }
     hip_check(hipMemcpy(out.data(), d_dst, out.size(), hipMemcpyDeviceToHost), "D2H");
     std::vector<std::vector<uint8_t>> pkts(n);
     for (size_t i = 0; i < n; ++i)

@@ -864,6 +864,75 @@ int ingot_gpu_emit_headers(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_
                            const uint64_t* d_out_off, uint32_t out_stride, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Emit with checksums: ingot_gpu_emit_packets that also fills the outer IPv4
+ * header checksum and / or the outer UDP checksum of every packet it writes,
+ * in the same launch (the kernel holds every output byte in registers, so the
+ * payload is not read a second time).  One call instead of emit_packets + a
+ * UDP_PARSER parse of the result + ingot_gpu_checksum_fill.  Build-defined,
+ * like the checksum calls; tests/emit_csum_model.py is the definition.
+ *
+ * In emit's spirit nothing is derived: the caller names each sum (`sums`,
+ * n_sums <= INGOT_MAX_EMIT_SUMS, host memory, at most one of each kind).
+ * The emitted bytes are exactly those of ingot_gpu_emit_packets with the same
+ * arguments, except the two checksum-field bytes of each named sum, which are
+ * computed after all setters of that packet have been applied (a setter that
+ * targets a checksum field is overridden).  n_sums == 0 is byte-identical to
+ * ingot_gpu_emit_packets.  The IPV4 sum is written before the UDP sum is
+ * taken, so a UDP segment that covers the named IPv4 header sums its final
+ * bytes.
+ *
+ *   INGOT_EMIT_SUM_IPV4  the field at `at + 10`: the RFC 1071 checksum of
+ *       [at, at + 4 * ihl) of the packet's patched header block, the field
+ *       taken as 0; ihl is read from the host block `hdr` at call time.
+ *   INGOT_EMIT_SUM_UDP   the field at `at + 6`: the segment is every emitted
+ *       byte from `at` to the packet's end, S = hdr_len + d_len[i] - at bytes
+ *       (an odd last byte padded with 0, the field taken as 0), plus the
+ *       pseudo-header taken from the packet's patched header at `l3_at`
+ *       (per-packet address setters are honoured).  The IP version is
+ *       hdr[l3_at] >> 4 of the host block: IPv4 = source, destination, 0, 17,
+ *       S as 16 bits; IPv6 = source, destination, S as 32 bits, next header
+ *       17 (the constant 17 even when extension headers sit between).  A
+ *       result of 0 is written as 0xffff (RFC 768).  S > 65535: no such
+ *       datagram exists, and the field keeps the bytes the header block and
+ *       the setters gave it.
+ *
+ * EINVAL, besides ingot_gpu_emit_packets's own: n_sums too large or sums NULL
+ * with n_sums > 0; an unknown kind, non-zero padding, two sums of one kind; an
+ * odd `at` or `l3_at` (every stack ingot can serialise keeps its headers at
+ * even offsets); IPV4: l3_at != 0, version nibble != 4, ihl < 5, at + 4 * ihl
+ * > hdr_len; UDP: at + 8 > hdr_len, version nibble at l3_at not 4 or 6, the IP
+ * header's fixed part (20 / 40 B) not ending at or before `at`; a setter on
+ * V4_VERSION, V4_IHL or V6_VERSION of a header that a sum names (the IPV4
+ * sum's `at`, the UDP sum's `l3_at`).  So hdr_len == 0 with sums is EINVAL.
+ * ERANGE from the LDS-fit check as in ingot_gpu_emit_packets.
+ *
+ * Out of scope: sums in ingot_gpu_emit_headers (that kernel never sees the
+ * payload); inner-frame checksums (ingot_gpu_checksum_fill on the source
+ * arena before the emit); TCP and ICMP kinds.
+ * ------------------------------------------------------------------------- */
+enum ingot_emit_sum_kind { INGOT_EMIT_SUM_IPV4 = 0, INGOT_EMIT_SUM_UDP = 1 };
+#define INGOT_MAX_EMIT_SUMS 2
+
+typedef struct ingot_emit_sum {
+    uint16_t at;     /* byte offset in hdr of the header that holds the checksum field */
+    uint16_t l3_at;  /* UDP: byte offset in hdr of the IPv4 / IPv6 header whose addresses
+                        form the pseudo-header; IPV4: must be 0 */
+    uint8_t kind;    /* enum ingot_emit_sum_kind */
+    uint8_t _pad[3]; /* must be 0 */
+} ingot_emit_sum;
+
+#ifdef __cplusplus
+static_assert(sizeof(ingot_emit_sum) == 8, "ingot_emit_sum is 8 bytes");
+#endif
+
+int ingot_gpu_emit_packets_csum(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
+                                const ingot_emit_set* sets, uint32_t n_sets,
+                                const ingot_emit_sum* sums, uint32_t n_sums,
+                                const uint8_t* d_src, const uint64_t* d_off,
+                                const uint16_t* d_len, uint64_t n, uint8_t* d_dst,
+                                const uint64_t* d_dst_off, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Internet checksums (RFC 1071) of already parsed frames: verify or fill the
  * IPv4 header checksum and the TCP / UDP / ICMPv4 / ICMPv6 checksum of every
  * packet of a batch, on the device.  Build-defined, like the flow hash: ingot

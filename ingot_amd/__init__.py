@@ -55,10 +55,12 @@ from .abi import (  # noqa: F401  (re-exports)
     L4Kind,
     EditOp,
     EmitSource,
+    EmitSum,
     Field,
     ParseError,
     edits_array,
     emit_sets_array,
+    emit_sums_array,
     rec16_to_rec8,
 )
 
@@ -67,7 +69,7 @@ __all__ = [
     "GenericUlp", "VlanUlp", "GeneveOverV6Tunnel", "gen_frames", "gen_lengths", "records_to_numpy",
     "fields_to_numpy", "load_library", "Parsed", "chunk_tables", "HeaderKind", "parse_header",
     "HeaderParseError", "first_chunks", "CsumState", "CSUM_L3", "CSUM_L4", "CSUM_OUTER_L4",
-    "CSUM_DTYPE",
+    "CSUM_DTYPE", "EmitSum",
 ]
 
 
@@ -516,12 +518,17 @@ class Context:
             rows.append((e[0], e[1], e[2], e[3], None if vals is None else vals.data_ptr()))
         return emit_sets_array(rows), keep
 
-    def emit_packets(self, hdr: bytes, sets, src, off, lens, dst, dst_off, stream=None):
+    def emit_packets(self, hdr: bytes, sets, src, off, lens, dst, dst_off, stream=None,
+                     sums=None):
         """Batched Emit (ingot_gpu_emit_packets): packet i = the header block
         `hdr` (owned headers serialised once on the host, e.g. by emit_headers
         below) with the per-packet setters `sets` applied, then src[off[i] ..
         + lens[i]), written at dst + dst_off[i].  sets = [(at, Field,
-        EmitSource, add[, per-packet u16/u32 cuda tensor]), ...]."""
+        EmitSource, add[, per-packet u16/u32 cuda tensor]), ...].
+
+        sums (ingot_gpu_emit_packets_csum) = [(EmitSum.UDP, at, l3_at),
+        (EmitSum.IPV4, at)]: the named outer checksums are filled in the same
+        launch, after the setters.  None calls the plain entry point."""
         n = off.numel()
         hdr = bytes(hdr)
         self._arg("src", src, _U8)
@@ -532,6 +539,14 @@ class Context:
         self._on_device(src=src, off=off, lens=lens, dst=dst, dst_off=dst_off)
         s, keep = self._emit_sets(sets, n)
         h = (ctypes.c_uint8 * max(len(hdr), 1)).from_buffer_copy(hdr or b"\0")
+        if sums is not None:
+            cs = emit_sums_array(sums)
+            _lib.check(self._lib.ingot_gpu_emit_packets_csum(
+                self._h, ctypes.addressof(h), len(hdr), s.ctypes.data_as(ctypes.c_void_p), len(s),
+                cs.ctypes.data_as(ctypes.c_void_p), len(cs), _ptr(src), _ptr(off), _ptr(lens), n,
+                _ptr(dst), _ptr(dst_off), _stream(stream, self.device)),
+                "ingot_gpu_emit_packets_csum")
+            return dst
         _lib.check(self._lib.ingot_gpu_emit_packets(
             self._h, ctypes.addressof(h), len(hdr), s.ctypes.data_as(ctypes.c_void_p), len(s),
             _ptr(src), _ptr(off), _ptr(lens), n, _ptr(dst), _ptr(dst_off),

@@ -380,6 +380,34 @@ def emit_sets_array(sets) -> np.ndarray:
     return a
 
 
+class EmitSum(enum.IntEnum):
+    """enum ingot_emit_sum_kind: a checksum ingot_gpu_emit_packets_csum fills."""
+
+    IPV4 = 0  # the IPv4 header checksum of the header at `at`
+    UDP = 1   # the UDP checksum of the header at `at`, pseudo-header from `l3_at`
+
+
+MAX_EMIT_SUMS = 2
+
+
+class IngotEmitSum(ctypes.Structure):
+    _fields_ = [("at", U16), ("l3_at", U16), ("kind", U8), ("_pad", U8 * 3)]
+
+
+assert ctypes.sizeof(IngotEmitSum) == 8
+EMIT_SUM_DTYPE = np.dtype([("at", "<u2"), ("l3_at", "<u2"), ("kind", "u1"), ("_pad", "u1", (3,))])
+assert EMIT_SUM_DTYPE.itemsize == 8
+
+
+def emit_sums_array(sums) -> np.ndarray:
+    """[(EmitSum, at[, l3_at]), ...] -> ingot_emit_sum array."""
+    a = np.zeros(len(sums), dtype=EMIT_SUM_DTYPE)
+    for k, e in enumerate(sums):
+        a[k]["kind"], a[k]["at"] = int(e[0]), e[1]
+        a[k]["l3_at"] = e[2] if len(e) > 2 else 0
+    return a
+
+
 class CsumState(enum.IntEnum):
     """enum ingot_csum_state: what ingot_gpu_checksum_verify / _fill say of a layer."""
 

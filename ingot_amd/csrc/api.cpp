@@ -746,22 +746,61 @@ int emit_args(const uint8_t* hdr, uint32_t hdr_len, const ingot_emit_set* sets,
     return INGOT_GPU_SUCCESS;
 }
 
+// ingot_gpu_emit_packets_csum: the sums, checked against the header block and
+// the setters that emit_args has already accepted into `a`.
+int emit_sums(const uint8_t* hdr, uint32_t hdr_len, const ingot_emit_set* sets, uint32_t n_sets,
+              const ingot_emit_sum* sums, uint32_t n_sums, ingot_gpu::EmitArgs& a) {
+    if (n_sums > INGOT_MAX_EMIT_SUMS || (n_sums && !sums)) return INGOT_GPU_EINVAL;
+    for (uint32_t k = 0; k < n_sums; ++k) {
+        const ingot_emit_sum& s = sums[k];
+        if (s.kind > INGOT_EMIT_SUM_UDP || s._pad[0] || s._pad[1] || s._pad[2] || (s.at & 1u) ||
+            (s.l3_at & 1u))
+            return INGOT_GPU_EINVAL;
+        const uint32_t at = s.at, l3 = s.l3_at;
+        uint32_t named;  // the header whose version / ihl this sum takes from hdr
+        if (s.kind == INGOT_EMIT_SUM_IPV4) {
+            if (a.sums.v4 || l3 != 0 || at + 20u > hdr_len) return INGOT_GPU_EINVAL;
+            const uint32_t ihl = hdr[at] & 0xfu;
+            if ((hdr[at] >> 4) != 4 || ihl < 5 || at + 4u * ihl > hdr_len) return INGOT_GPU_EINVAL;
+            a.sums.v4 = 1;
+            a.sums.v4_at = s.at;
+            a.sums.v4_len = (uint16_t)(4u * ihl);
+            named = at;
+        } else {
+            if (a.sums.udp || at + 8u > hdr_len || l3 >= hdr_len) return INGOT_GPU_EINVAL;
+            const uint32_t version = hdr[l3] >> 4;
+            if (version != 4 && version != 6) return INGOT_GPU_EINVAL;
+            if (l3 + (version == 4 ? 20u : 40u) > at) return INGOT_GPU_EINVAL;
+            a.sums.udp = 1;
+            a.sums.udp_v6 = version == 6;
+            a.sums.udp_at = s.at;
+            a.sums.udp_l3 = s.l3_at;
+            named = l3;
+        }
+        for (uint32_t e = 0; e < n_sets; ++e)
+            if (sets[e].at == named &&
+                (sets[e].field == INGOT_F_V4_VERSION || sets[e].field == INGOT_F_V4_IHL ||
+                 sets[e].field == INGOT_F_V6_VERSION))
+                return INGOT_GPU_EINVAL;
+    }
+    return INGOT_GPU_SUCCESS;
+}
+
 // The device's LDS per workgroup must hold one emit block's (ERANGE if not).
 int emit_fits(const ingot_gpu_ctx* ctx, const ingot_gpu::EmitArgs& a) {
     return ingot_gpu::emit_lds_bytes(a) <= ctx->lds_bytes ? INGOT_GPU_SUCCESS : INGOT_GPU_ERANGE;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ingot_gpu_emit_packets(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
-                           const ingot_emit_set* sets, uint32_t n_sets, const uint8_t* d_src,
-                           const uint64_t* d_off, const uint16_t* d_len, uint64_t n,
-                           uint8_t* d_dst, const uint64_t* d_dst_off, void* stream) {
+// Both whole-packet calls (the plain one: no sums).
+int emit_packets(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
+                 const ingot_emit_set* sets, uint32_t n_sets, const ingot_emit_sum* sums,
+                 uint32_t n_sums, const uint8_t* d_src, const uint64_t* d_off,
+                 const uint16_t* d_len, uint64_t n, uint8_t* d_dst, const uint64_t* d_dst_off,
+                 void* stream) {
     if (!ctx) return INGOT_GPU_EINVAL;
     ingot_gpu::EmitArgs a{};
     if (int e = emit_args(hdr, hdr_len, sets, n_sets, a)) return e;
+    if (int e = emit_sums(hdr, hdr_len, sets, n_sets, sums, n_sums, a)) return e;
     if (n == 0) return INGOT_GPU_SUCCESS;
     if (!d_src || !d_off || !d_len || !d_dst || !d_dst_off) return INGOT_GPU_EINVAL;
     if (int e = enter(ctx)) return e;
@@ -773,6 +812,27 @@ int ingot_gpu_emit_packets(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_
     a.n = n;
     if (int e = emit_fits(ctx, a)) return e;
     return from_hip(ingot_gpu::launch_emit(a, (hipStream_t)stream));
+}
+
+}  // namespace
+
+extern "C" {
+
+int ingot_gpu_emit_packets(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
+                           const ingot_emit_set* sets, uint32_t n_sets, const uint8_t* d_src,
+                           const uint64_t* d_off, const uint16_t* d_len, uint64_t n,
+                           uint8_t* d_dst, const uint64_t* d_dst_off, void* stream) {
+    return emit_packets(ctx, hdr, hdr_len, sets, n_sets, nullptr, 0, d_src, d_off, d_len, n,
+                        d_dst, d_dst_off, stream);
+}
+
+int ingot_gpu_emit_packets_csum(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
+                                const ingot_emit_set* sets, uint32_t n_sets,
+                                const ingot_emit_sum* sums, uint32_t n_sums, const uint8_t* d_src,
+                                const uint64_t* d_off, const uint16_t* d_len, uint64_t n,
+                                uint8_t* d_dst, const uint64_t* d_dst_off, void* stream) {
+    return emit_packets(ctx, hdr, hdr_len, sets, n_sets, sums, n_sums, d_src, d_off, d_len, n,
+                        d_dst, d_dst_off, stream);
 }
 
 int ingot_gpu_emit_headers(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,

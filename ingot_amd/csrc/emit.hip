@@ -1,4 +1,5 @@
-// emit.hip — batched Emit (ingot_gpu_emit_packets / ingot_gpu_emit_headers).
+// emit.hip — batched Emit (ingot_gpu_emit_packets / ingot_gpu_emit_headers /
+// ingot_gpu_emit_packets_csum: the SUMS instantiation, described where it starts).
 //
 // ingot's Emit (ingot-types/src/emit.rs:8-120) writes an owned header stack
 // field by field (the generated emit_raw, ingot-macros/src/packet/mod.rs:
@@ -165,8 +166,54 @@ __device__ __forceinline__ void store_edge(uint8_t* p, const u32x4& v, int32_t t
     }
 }
 
-template <bool COPY>
+// --- ingot_gpu_emit_packets_csum (the SUMS instantiation) -------------------
+// Sums are kept as the 16-bit words of aligned dwords added as loaded (the
+// sum is byte-order independent); a segment's big-endian sum is the folded
+// value, byte-swapped unless the segment starts at an odd address.
+__device__ __forceinline__ uint32_t fold16(uint32_t x) {
+    x = (x & 0xffffu) + (x >> 16);
+    return (x & 0xffffu) + (x >> 16);
+}
+__device__ __forceinline__ uint32_t swap16(uint32_t x) { return ((x & 0xffu) << 8) | (x >> 8); }
+__device__ __forceinline__ uint32_t below(int32_t k) {  // bytes [0, k) of a dword, k any integer
+    return k >= 4 ? 0xffffffffu : k <= 0 ? 0u : ((1u << (8u * (uint32_t)k)) - 1u);
+}
+// Bytes [b0, b1) of a 16-B chunk: its 16-bit words as loaded, added.
+__device__ __forceinline__ uint32_t chunk_words(const u32x4& v, int32_t b0, int32_t b1) {
+    const uint32_t x = v.x & below(b1) & ~below(b0), y = v.y & below(b1 - 4) & ~below(b0 - 4),
+                   z = v.z & below(b1 - 8) & ~below(b0 - 8), w = v.w & below(b1 - 12) & ~below(b0 - 12);
+    return (x & 0xffffu) + (x >> 16) + (y & 0xffffu) + (y >> 16) + (z & 0xffffu) + (z >> 16) +
+           (w & 0xffffu) + (w >> 16);
+}
+// The same over bytes [b0, b1) of a packet's region (LDS, 16-B aligned).
+__device__ __forceinline__ uint32_t region_words(const uint8_t* R, uint32_t b0, uint32_t b1) {
+    uint32_t s = 0;
+    for (uint32_t d = b0 >> 2; 4u * d < b1; ++d) {
+        const int32_t o = (int32_t)(4u * d);
+        const uint32_t x = reinterpret_cast<const uint32_t*>(R)[d] & below((int32_t)b1 - o) &
+                           ~below((int32_t)b0 - o);
+        s += (x & 0xffffu) + (x >> 16);
+    }
+    return s;
+}
+// Byte `pos` of a chunk := val, when the chunk holds it (0 <= pos < 16).
+__device__ __forceinline__ void put_byte(u32x4& v, int32_t pos, uint32_t val) {
+    if (pos < 0 || pos > 15) return;
+    const uint32_t d = (uint32_t)pos >> 2, sh = 8u * ((uint32_t)pos & 3u);
+    const uint32_t m = 0xffu << sh, b = val << sh;
+    v.x = d == 0 ? (v.x & ~m) | b : v.x;
+    v.y = d == 1 ? (v.y & ~m) | b : v.y;
+    v.z = d == 2 ? (v.z & ~m) | b : v.z;
+    v.w = d == 3 ? (v.w & ~m) | b : v.w;
+}
+// Per-packet LDS of the UDP sum: the packet's accumulator and the one or two
+// chunks that hold the checksum field (two when its bytes straddle a 16-B
+// destination boundary), parked until the sum is known.
+constexpr uint32_t SUM_LDS_PER_PACKET = 4u + 2u * 16u;
+
+template <bool COPY, bool SUMS = false>
 __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
+    static_assert(COPY || !SUMS, "sums need the payload: whole packets only");
     constexpr uint32_t BLOCK = Shape<COPY>::BLOCK, W = Shape<COPY>::W, G = Shape<COPY>::G;
     constexpr uint32_t PW = Shape<COPY>::PW, NP = Shape<COPY>::NP;
     constexpr uint32_t NPOW = NP <= 64 ? 64 : NP <= 128 ? 128 : 256;  // search span
@@ -187,6 +234,11 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
     const uint32_t wg = (threadIdx.x / WAVE) % W;  // this wave's turn in its group
     Desc& wd = reinterpret_cast<Desc*>(smem + TB * 16)[g];
     uint8_t* regions = smem + TB * 16 + G * sizeof(Desc) + g * NP * RS;
+    // SUMS (G == 1): after the regions, the parked chunks, then the accumulators
+    u32x4* park = reinterpret_cast<u32x4*>(smem + TB * 16 + G * sizeof(Desc) + G * NP * RS);
+    uint32_t* acc = reinterpret_cast<uint32_t*>(park + 2u * NP);
+    const bool udp = SUMS && a.sums.udp;
+    const uint32_t fpos = (uint32_t)a.sums.udp_at + 6u;  // the UDP checksum field in hdr
     __syncthreads();
     const uint64_t base = ((uint64_t)blockIdx.x * G + g) * NP;
     if (wg < PW) {
@@ -229,6 +281,40 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
                     uint8_t& b = R[dmis + e.pos + k];
                     b = (uint8_t)((b & ~(m >> shb)) | ((vb >> shb) & (m >> shb)));
                 }
+            }
+        }
+
+        if constexpr (SUMS) {
+            // 2b. the sums of what this lane just patched.  IPv4: complete, and
+            //     written into the region before anything reads it (so a UDP
+            //     segment that covers the header sums the final bytes).  UDP:
+            //     the header bytes of the segment [udp_at, H) without the
+            //     field, and the pseudo-header, start the packet's accumulator;
+            //     the walkers add the payload.  All of it has the parity of
+            //     the destination address (`at` and `l3_at` are even).
+            const uint32_t odd = dmis & 1u;
+            if (live && a.sums.v4) {
+                const uint32_t b0 = dmis + a.sums.v4_at;
+                R[b0 + 10] = 0;
+                R[b0 + 11] = 0;
+                const uint32_t f = fold16(region_words(R, b0, b0 + a.sums.v4_len));
+                const uint32_t c = ~(odd ? f : swap16(f)) & 0xffffu;
+                R[b0 + 10] = (uint8_t)(c >> 8);
+                R[b0 + 11] = (uint8_t)c;
+            }
+            if (a.sums.udp) {
+                uint32_t s = 0;
+                if (live) {
+                    const uint32_t b0 = dmis + a.sums.udp_at, l3 = dmis + a.sums.udp_l3;
+                    const uint32_t seg = H + L - a.sums.udp_at;  // > 65535: never written
+                    const uint32_t tail = fold16(seg + 17u);     // length and next header / protocol
+                    s = region_words(R, b0, dmis + H) - ((uint32_t)R[b0 + 6] << (8u * odd)) -
+                        ((uint32_t)R[b0 + 7] << (8u * (odd ^ 1u))) +
+                        (a.sums.udp_v6 ? region_words(R, l3 + 8u, l3 + 40u)
+                                       : region_words(R, l3 + 12u, l3 + 20u)) +
+                        (odd ? tail : swap16(tail));
+                }
+                acc[j] = s;
             }
         }
 
@@ -282,6 +368,7 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
         uint32_t q[U], c[U];
         u32x4 own[U], nb[U];
         bool extra[U];
+        bool last[U];  // SUMS: the wave's last chunk of its packet in this step
 #pragma unroll
         for (uint32_t u = 0; u < U; ++u) {
             const uint32_t k = k0 + u * WAVE + lane;
@@ -303,6 +390,7 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
                 c[u] = valid ? k - qq * CP : 0xffffu;
             }
             q[u] = qq;
+            last[u] = SUMS && valid && (lane == WAVE - 1 || k + 1 >= end);
             own[u] = u32x4{0u, 0u, 0u, 0u};
             nb[u] = u32x4{0u, 0u, 0u, 0u};
             extra[u] = false;
@@ -350,7 +438,29 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
                 out.z = (hb.z & m2) | (out.z & ~m2);
                 out.w = (hb.w & m3) | (out.w & ~m3);
             }
-            if (valid) {
+            bool parked = false;
+            if constexpr (SUMS) {
+                if (udp) {
+                    // the payload bytes of this chunk, [p0, p1): their words as
+                    // loaded; a segmented inclusive scan over the wave (the
+                    // lanes of a packet are contiguous, chunk c[u] is c[u]
+                    // lanes after its packet's first) leaves the packet's share
+                    // of this step in its last lane, which adds it in LDS
+                    const int32_t p0 = max((int32_t)H - r0, 0), p1 = min((int32_t)QT - r0, 16);
+                    uint32_t s = (valid && p0 < p1) ? chunk_words(out, p0, p1) : 0u;
+#pragma unroll
+                    for (uint32_t o = 1; o < WAVE; o <<= 1) {
+                        const uint32_t y = (uint32_t)__shfl_up((int)s, o);
+                        if (lane >= o && o <= c[u]) s += y;
+                    }
+                    if (last[u] && s) atomicAdd(&acc[qq], s);
+                    // the chunk(s) holding the field wait in LDS for the sum
+                    const uint32_t cf = (qd + fpos) >> 4;
+                    parked = valid && (c[u] == cf || c[u] == ((qd + fpos + 1u) >> 4));
+                    if (parked) park[(c[u] - cf) * NP + qq] = out;
+                }
+            }
+            if (valid && !parked) {
                 const int32_t t0 = r0 < 0 ? -r0 : 0;
                 const int32_t t1 = (int32_t)QT - r0 < 16 ? (int32_t)QT - r0 : 16;
                 if (t0 == 0 && t1 == 16) {
@@ -361,38 +471,78 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
             }
         }
     }
+    if constexpr (SUMS) {
+        if (!udp) return;
+        // 5. every chunk is summed once the block is here.  One lane per parked
+        //    chunk: fold the packet's sum, put the field's byte(s) that lie in
+        //    this chunk, and issue the chunk's only store.
+        __syncthreads();
+        if (threadIdx.x >= 2u * NP) return;
+        const uint32_t slot = threadIdx.x / NP, j = threadIdx.x % NP;
+        if (base + j >= a.n) return;
+        const uint32_t qd = wd.mis[j] & 0xffu;
+        const uint32_t cf = (qd + fpos) >> 4;
+        if (slot && ((qd + fpos + 1u) >> 4) == cf) return;  // the field sits in one chunk
+        const uint32_t c = cf + slot;
+        u32x4 out = park[slot * NP + j];
+        const uint32_t QT = H + wd.len[j];
+        if (QT - a.sums.udp_at <= 65535u) {
+            const uint32_t f = fold16(acc[j]);
+            uint32_t sum = ~((qd & 1u) ? f : swap16(f)) & 0xffffu;
+            sum = sum ? sum : 0xffffu;
+            const int32_t pos = (int32_t)(qd + fpos) - (int32_t)(16u * c);
+            put_byte(out, pos, sum >> 8);
+            put_byte(out, pos + 1, sum & 0xffu);
+        }
+        uint8_t* QD = (uint8_t*)(uintptr_t)wd.dst[j];
+        const int32_t r0 = (int32_t)(16u * c) - (int32_t)qd;
+        const int32_t t0 = r0 < 0 ? -r0 : 0;
+        const int32_t t1 = (int32_t)QT - r0 < 16 ? (int32_t)QT - r0 : 16;
+        if (t0 == 0 && t1 == 16) {
+            *(__attribute__((address_space(1))) u32x4*)(QD + r0) = out;
+        } else {
+            store_edge(QD + r0, out, t0, t1);
+        }
+    }
 }
 
 // Dynamic LDS of one k_emit block for a header block of H bytes.
-template <bool COPY>
+template <bool COPY, bool SUMS = false>
 constexpr size_t emit_smem(uint32_t H) {
     return (INGOT_MAX_EMIT_HDR / 16 + 4) * 16 +
-           Shape<COPY>::G * (sizeof(WaveDesc<Shape<COPY>::NP>) + Shape<COPY>::NP * region_bytes(H));
+           Shape<COPY>::G * (sizeof(WaveDesc<Shape<COPY>::NP>) + Shape<COPY>::NP * region_bytes(H)) +
+           (SUMS ? Shape<COPY>::NP * SUM_LDS_PER_PACKET : 0u);
 }
 // gfx950: 160 KiB of LDS per workgroup.  A build with other group shapes
 // (INGOT_EMIT_GROUP_SUBS / _WAVES) must still fit the largest header block.
 static_assert(emit_smem<true>(INGOT_MAX_EMIT_HDR) <= 160u * 1024u, "k_emit<copy> LDS > 160 KiB");
 static_assert(emit_smem<false>(INGOT_MAX_EMIT_HDR) <= 160u * 1024u, "k_emit LDS > 160 KiB");
+static_assert(emit_smem<true, true>(INGOT_MAX_EMIT_HDR) <= 160u * 1024u,
+              "k_emit<copy, sums> LDS > 160 KiB");
+static_assert(Shape<true>::G == 1 && Shape<true>::BLOCK >= 2 * Shape<true>::NP,
+              "sums: one group per block, one lane per parked chunk");
 
-template <bool COPY>
+template <bool COPY, bool SUMS = false>
 hipError_t go(const EmitArgs& a, hipStream_t s) {
     constexpr uint32_t G = Shape<COPY>::G, NP = Shape<COPY>::NP;
     const uint64_t groups = (a.n + NP - 1) / NP;
     const uint64_t blocks = (groups + G - 1) / G;
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    const size_t smem = emit_smem<COPY>(a.hdr_len);
-    hipLaunchKernelGGL((k_emit<COPY>), dim3((uint32_t)blocks), dim3(Shape<COPY>::BLOCK), smem, s, a);
+    const size_t smem = emit_smem<COPY, SUMS>(a.hdr_len);
+    hipLaunchKernelGGL((k_emit<COPY, SUMS>), dim3((uint32_t)blocks), dim3(Shape<COPY>::BLOCK), smem, s, a);
     return hipGetLastError();
 }
 
 }  // namespace
 
 size_t emit_lds_bytes(const EmitArgs& a) {
+    if (a.sums.v4 || a.sums.udp) return emit_smem<true, true>(a.hdr_len);
     return a.src ? emit_smem<true>(a.hdr_len) : emit_smem<false>(a.hdr_len);
 }
 
 hipError_t launch_emit(const EmitArgs& a, hipStream_t s) {
     if (a.n == 0) return hipSuccess;
+    if (a.sums.v4 || a.sums.udp) return a.src ? go<true, true>(a, s) : hipErrorInvalidValue;
     return a.src ? go<true>(a, s) : go<false>(a, s);
 }
 

@@ -165,6 +165,15 @@ struct EmitArgs {
     uint32_t n_sets;
     EmitSet sets[INGOT_MAX_EMIT_SETS];
     uint32_t hdr[INGOT_MAX_EMIT_HDR / 4];  // the header block, zero-padded
+    // ingot_gpu_emit_packets_csum: the validated sums, after everything else
+    // so the plain emit kernels read their arguments where they always did.
+    // Both absent: the plain kernels run.
+    struct Sums {
+        uint16_t v4_at, v4_len;    // IPV4: the header in hdr, its 4 * ihl bytes
+        uint16_t udp_at, udp_l3;   // UDP: the UDP header, the IP header of the pseudo-header
+        uint8_t v4, udp, udp_v6;   // which sums; the pseudo-header's IP version is 6
+        uint8_t _pad;
+    } sums;
 };
 static_assert(sizeof(EmitArgs) <= 4096, "EmitArgs exceeds the 4 KiB kernel-argument limit");
 // bytes of dynamic LDS one emit block needs (checked against the device)

@@ -10,9 +10,12 @@ flow bins from k_flows_bits and from k_parse's flows mode, the slot ring, and
 the checksum calls (`csum`: verify, then fill + verify, against the Python
 model of tests/csum_model.py, so on at most --csum-frames frames per case),
 and the rewrite with the fused checksum update (`modify_csum`: against the
-oracle's rewrite + the Python model of tests/csum_update_model.py, same cap).
+oracle's rewrite + the Python model of tests/csum_update_model.py, same cap),
+and the emit with checksums (`emit_csum`: against the oracle's emit + the
+Python model of tests/emit_csum_model.py, same cap).
 
-    python tools/bigfuzz.py [--frames 4000000] [--seed 1234] [--only csum|modify_csum]
+    python tools/bigfuzz.py [--frames 4000000] [--seed 1234]
+                            [--only csum|modify_csum|emit_csum]
 """
 from __future__ import annotations
 
@@ -151,6 +154,51 @@ def modify_csum_cases(ctx, n, seed, res):
         torch.cuda.empty_cache()
 
 
+def emit_csum_cases(ctx, n, seed, res):
+    """ingot_gpu_emit_packets_csum against the oracle's emit followed by the
+    model: every header stack of tests/emit_csum_cases.py in front of the
+    frames of four generator profiles, packed with 0-3 B gaps; the whole
+    destination arena is compared."""
+    import torch
+
+    import ingot_amd
+    import oracle
+    from ingot_amd import GenProfile
+    from tests import emit_csum_cases as cases
+    from tests import emit_csum_model as model
+
+    def dev(a):
+        a = np.ascontiguousarray(a)
+        signed = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32,
+                  np.dtype(np.uint64): np.int64}
+        return torch.from_numpy(a.view(signed.get(a.dtype, a.dtype))).cuda()
+
+    rng = np.random.default_rng(seed)
+    profiles = (GenProfile.MIXED, GenProfile.VLAN_V6EH, GenProfile.ADVERSARIAL, GenProfile.GENEVE)
+    for k, prof in enumerate(profiles):
+        arena, off, lens = ingot_amd.gen_frames(prof, n, seed=seed + 110 + k)
+        a, o, ln = arena.cpu().numpy(), off.cpu().numpy().view(np.uint64), lens.cpu().numpy()
+        for name in cases.STACKS:
+            hdr, sets, sums = cases.stack(name, n, rng)
+            dst_off, size = cases.pack(ln, len(hdr), rng)
+            dst = dev(np.full(size, 0xA5, np.uint8))
+            dsets = [s if len(s) == 4 else (*s[:4], dev(s[4])) for s in sets]
+            ctx.emit_packets(hdr, dsets, arena, off, lens, dst, dev(dst_off), sums=sums)
+            torch.cuda.synchronize()
+            want = np.full(size, 0xA5, np.uint8)
+            oracle.emit_batch(hdr, sets, a, o, ln, want, dst_off, nthreads=16)
+            plain = want.copy()
+            model.apply(want, hdr, sums, dst_off, ln, sets)
+            key = f"emit_csum/{prof.name}/{name}"
+            res[key] = {"byte_mismatches": int((dst.cpu().numpy() != want).sum()),
+                        "checksum_bytes_moved": int((want != plain).sum()),
+                        "arena_bytes": size}
+            print(key, res[key], flush=True)
+            del dst
+        del arena, off, lens
+        torch.cuda.empty_cache()
+
+
 def finish(n, seed, t0, res):
     out = {"frames_per_case": n, "seed": seed, "wall_s": round(time.time() - t0, 1),
            "cases": res,
@@ -167,13 +215,14 @@ def main():
     ap.add_argument("--csum-frames", type=int, default=200_000,
                     help="frames per csum case (its reference is a Python model)")
     ap.add_argument("--only", default="",
-                    help="'csum' / 'modify_csum': run only that case group")
+                    help="'csum' / 'modify_csum' / 'emit_csum': run only that case group")
     args = ap.parse_args()
-    if args.only in ("csum", "modify_csum"):
+    if args.only in ("csum", "modify_csum", "emit_csum"):
         import ingot_amd
 
         res, t0 = {}, time.time()
-        group = csum_cases if args.only == "csum" else modify_csum_cases
+        group = {"csum": csum_cases, "modify_csum": modify_csum_cases,
+                 "emit_csum": emit_csum_cases}[args.only]
         group(ingot_amd.Context(0), min(args.frames, args.csum_frames), args.seed, res)
         return finish(min(args.frames, args.csum_frames), args.seed, t0, res)
 
