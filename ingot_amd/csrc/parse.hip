@@ -177,7 +177,8 @@ __global__ __launch_bounds__(BLOCK) void k_parse(ARGS args) {
             if (valid) store_rec(static_cast<uint2*>(a.out) + i, pack8(r), a.policy);
         } else if constexpr (MODE == OUT_MODIFY) {
             // parse, then the setters in order (each sees the previous
-            // edits' bytes: put8 updates HBM and the staged window)
+            // edits' bytes: staged ones in the window, whose sectors may be
+            // written back only after the loop, the others in HBM)
             walk<CHAIN, false>(fr, r, nullptr, nullptr);
             if (valid && r.status == INGOT_OK) {
                 EditSink sink{const_cast<uint8_t*>(a.arena) + off, off, base, len, NCH ? nch : 0u,

@@ -445,8 +445,9 @@ __global__ __launch_bounds__(BLOCK) void k_modify_pipe(ARGS args) {
                 uint32_t h;
                 if (!header_at<CHAIN>(r, e.layer, e.kind, e.index, h)) continue;
                 // the setter (bitfield.rs:188-315): read-modify-write of the
-                // covering bytes through the staged copy
-                uint64_t w = fr.be(h + e.byte0, e.nbytes);
+                // covering bytes through the staged copy (a field across the
+                // window's end: each byte from its side, see be_edited)
+                uint64_t w = fr.be_edited(h + e.byte0, e.nbytes);
                 [[maybe_unused]] const uint32_t w_old = CSUM ? (uint32_t)w : 0u;
                 const uint32_t fm = e.bits >= 32 ? 0xffffffffu : ((1u << e.bits) - 1u);
                 const uint32_t cur = (uint32_t)(w >> e.rshift) & fm;

@@ -298,6 +298,21 @@ struct Frame {
         return (be(hdr + f.byte0(), f.nbytes()) >> f.rshift()) & f.mask();
     }
 
+    // be() / get() for the rewrite, where an earlier edit of the same launch
+    // may have written the bytes: a staged byte's newest value is in the
+    // staged copy (its sector may be written back only after all edits), a
+    // byte past the window has it in HBM.  be() reads a field that straddles
+    // the window's end wholly from HBM; here each byte comes from its side.
+    __device__ __forceinline__ uint32_t be_edited(uint32_t i, uint32_t n) const {
+        if (i + n <= avail || i >= avail) return be(i, n);
+        uint32_t v = 0;
+        for (uint32_t k = 0; k < n; ++k) v = (v << 8) | be(i + k, 1);
+        return v;
+    }
+    __device__ __forceinline__ uint32_t get_edited(uint32_t hdr, Field f) const {
+        return (be_edited(hdr + f.byte0(), f.nbytes()) >> f.rshift()) & f.mask();
+    }
+
     // Setter support: byte i of the frame in the staged copy (so a later
     // edit reads the new value) ...
     __device__ __forceinline__ void put_staged(uint32_t i, uint8_t v) const {
@@ -1067,7 +1082,7 @@ __device__ __forceinline__ void csum_finish(const FR& f, const Rec& r, uint32_t 
     if ((what & INGOT_CSUM_L4) && r.l4_kind != INGOT_L4_NONE) {
         // a non-first IPv4 fragment's bytes at l4_off are not an L4 header
         const bool later_frag =
-            r.l3_kind == INGOT_L3_IPV4 && f.get(r.l3_off, ipv4::fragment_offset) != 0u;
+            r.l3_kind == INGOT_L3_IPV4 && f.get_edited(r.l3_off, ipv4::fragment_offset) != 0u;
         const uint32_t at = r.l4_kind == INGOT_L4_TCP ? 16u : r.l4_kind == INGOT_L4_UDP ? 6u : 2u;
         if (!later_frag) update(r.l4_off + at, c.l4, r.l4_kind == INGOT_L4_UDP);
     }
@@ -1082,13 +1097,14 @@ __device__ __forceinline__ void csum_finish(const FR& f, const Rec& r, uint32_t 
 
 // One generated setter: read-modify-write of the field's covering bytes,
 // neighbouring bits preserved (bitfield.rs:188-315), big-endian.  The bytes
-// are read through the frame view (staged window first).
+// are read through the frame view (staged window first, byte by byte where
+// the field straddles its end: an earlier edit's bytes are on both sides).
 // CSUM: returns the bytes' RFC 1624 term (csum_term) for the fused checksum
 // update; otherwise 0.
 template <bool CSUM = false, class FR>
 __device__ __forceinline__ uint32_t apply_edit(const FR& f, EditSink& sink, uint32_t h,
                                                const Edit& e) {
-    uint64_t w = f.be(h + e.byte0, e.nbytes);  // fields span <= 4 bytes
+    uint64_t w = f.be_edited(h + e.byte0, e.nbytes);  // fields span <= 4 bytes
     [[maybe_unused]] const uint32_t w_old = (uint32_t)w;
     const uint32_t fm = e.bits >= 32 ? 0xffffffffu : ((1u << e.bits) - 1u);
     const uint32_t cur = (uint32_t)(w >> e.rshift) & fm;

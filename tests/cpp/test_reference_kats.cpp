@@ -432,27 +432,36 @@ TEST(bitset_fields_do_not_disturb_neighbours) {
 // ingot-examples/src/tests.rs:189-268: the reference tunnel frame's outer
 // stack emitted in front of its inner frame (batched, with OPTE's per-packet
 // setters) parses back as GeneveOverV6Tunnel with those values.
-TEST(encapsulate_and_parse_back) {
-    static const uint8_t frame[] = {
-        0xA8, 0x40, 0x25, 0x77, 0x77, 0x76, 0xA8, 0x40, 0x25, 0x77, 0x77, 0x77, 0x86, 0xDD,
-        0x60, 0x00, 0x00, 0x00, 0x00, 0x10, 0x11, 0xF0,
-        0xFD, 0x00, 0x00, 0x00, 0x00, 0xF7, 0x01, 0x01, 0, 0, 0, 0, 0, 0, 0, 0x02,
-        0xFD, 0x00, 0x00, 0x00, 0x00, 0xF7, 0x01, 0x01, 0, 0, 0, 0, 0, 0, 0, 0x01,
-        0x1E, 0x61, 0x17, 0xC1, 0x00, 0x14, 0x00, 0x00,
-        0x01, 0x00, 0x65, 0x58, 0x00, 0x04, 0xD2, 0x00, 0x01, 0x29, 0x00, 0x00,
-        0xAA, 0x00, 0x04, 0x00, 0xFF, 0x10, 0xAA, 0x00, 0x04, 0x00, 0xFF, 0x01, 0x08, 0x00,
-        0x45, 0x00, 0x00, 36, 0x00, 0x00, 0x00, 0x00, 0xF0, 0x11, 0x00, 0x00,
-        8, 8, 8, 8, 192, 168, 0, 5,
-        0x00, 0x80, 0x00, 53, 0x00, 0x08, 0x00, 0x00, 0, 1, 2, 3, 4, 5, 6, 7};
-    const std::vector<uint8_t> hdr(frame, frame + 74), inner(frame + 74, frame + sizeof(frame));
-    std::vector<std::vector<uint8_t>> payloads;
-    std::vector<uint32_t> ports, vnis;
+static const uint8_t kTunnelFrame[] = {
+    0xA8, 0x40, 0x25, 0x77, 0x77, 0x76, 0xA8, 0x40, 0x25, 0x77, 0x77, 0x77, 0x86, 0xDD,
+    0x60, 0x00, 0x00, 0x00, 0x00, 0x10, 0x11, 0xF0,
+    0xFD, 0x00, 0x00, 0x00, 0x00, 0xF7, 0x01, 0x01, 0, 0, 0, 0, 0, 0, 0, 0x02,
+    0xFD, 0x00, 0x00, 0x00, 0x00, 0xF7, 0x01, 0x01, 0, 0, 0, 0, 0, 0, 0, 0x01,
+    0x1E, 0x61, 0x17, 0xC1, 0x00, 0x14, 0x00, 0x00,
+    0x01, 0x00, 0x65, 0x58, 0x00, 0x04, 0xD2, 0x00, 0x01, 0x29, 0x00, 0x00,
+    0xAA, 0x00, 0x04, 0x00, 0xFF, 0x10, 0xAA, 0x00, 0x04, 0x00, 0xFF, 0x01, 0x08, 0x00,
+    0x45, 0x00, 0x00, 36, 0x00, 0x00, 0x00, 0x00, 0xF0, 0x11, 0x00, 0x00,
+    8, 8, 8, 8, 192, 168, 0, 5,
+    0x00, 0x80, 0x00, 53, 0x00, 0x08, 0x00, 0x00, 0, 1, 2, 3, 4, 5, 6, 7};
+
+// The 300 payloads of encapsulate_and_parse_back (the inner frame with 0-36
+// trailing bytes) and their per-packet entropy ports and VNIs.
+static void encap_inputs(std::vector<std::vector<uint8_t>>& payloads, std::vector<uint32_t>& ports,
+                         std::vector<uint32_t>& vnis) {
+    const std::vector<uint8_t> inner(kTunnelFrame + 74, kTunnelFrame + sizeof(kTunnelFrame));
     for (uint32_t i = 0; i < 300; ++i) {
         payloads.push_back(inner);
         payloads.back().resize(inner.size() + i % 37, (uint8_t)i);  // varied lengths
         ports.push_back(0xC000 | i);
         vnis.push_back(0x100000 + i);
     }
+}
+
+TEST(encapsulate_and_parse_back) {
+    const std::vector<uint8_t> hdr(kTunnelFrame, kTunnelFrame + 74);
+    std::vector<std::vector<uint8_t>> payloads;
+    std::vector<uint32_t> ports, vnis;
+    encap_inputs(payloads, ports, vnis);
     auto pkts = gpu::emit_batch(
         gpu::default_context(), hdr,
         {{14, INGOT_F_V6_PAYLOAD_LEN, INGOT_EMIT_LENGTH, -40, {}},
@@ -472,6 +481,154 @@ TEST(encapsulate_and_parse_back) {
         ASSERT_EQ(h.outer_udp.source(), (uint16_t)(0xC000 | i));
         ASSERT_EQ(h.outer_encap.vni(), 0x100000u + i);
         ASSERT_EQ(h.outer_udp.destination(), 6081);
+    }
+}
+
+// RFC 1071 byte by byte: big-endian 16-bit words (an odd last byte padded
+// with 0) added to `s` with end-around carry.  `p` starts at an even place of
+// the summed data.
+static uint32_t sum1071(const uint8_t* p, size_t n, uint32_t s = 0) {
+    for (size_t i = 0; i < n; ++i) s += (i & 1) ? (uint32_t)p[i] : (uint32_t)p[i] << 8;
+    while (s >> 16) s = (s & 0xffffu) + (s >> 16);
+    return s;
+}
+
+// The receiver's checks (RFC 1624: the sum over the covered bytes, the field
+// included, is 0xffff).  `l3` / `at`: the IP and L4 headers' offsets.
+static bool v4_header_ok(const std::vector<uint8_t>& p, size_t l3) {
+    return sum1071(&p[l3], (size_t)(p[l3] & 0xf) * 4) == 0xffffu;
+}
+static bool l4_ok(const std::vector<uint8_t>& p, size_t l3, size_t at, uint8_t proto) {
+    const uint32_t S = (uint32_t)(p.size() - at);
+    std::vector<uint8_t> pseudo;
+    if (p[l3] >> 4 == 4) {
+        pseudo.assign(p.begin() + (long)l3 + 12, p.begin() + (long)l3 + 20);
+        for (uint8_t b : {(uint8_t)0, proto, (uint8_t)(S >> 8), (uint8_t)S}) pseudo.push_back(b);
+    } else {
+        pseudo.assign(p.begin() + (long)l3 + 8, p.begin() + (long)l3 + 40);
+        for (uint8_t b : {(uint8_t)(S >> 24), (uint8_t)(S >> 16), (uint8_t)(S >> 8), (uint8_t)S,
+                          (uint8_t)0, (uint8_t)0, (uint8_t)0, proto})
+            pseudo.push_back(b);
+    }
+    return sum1071(&p[at], S, sum1071(pseudo.data(), pseudo.size())) == 0xffffu;
+}
+// Every byte of a and b outside [lo, lo + 2) for each listed `lo` is equal.
+static bool same_but(std::vector<uint8_t> a, std::vector<uint8_t> b,
+                     std::initializer_list<size_t> fields) {
+    if (a.size() != b.size()) return false;
+    for (size_t lo : fields) a[lo] = a[lo + 1] = b[lo] = b[lo + 1] = 0;
+    return a == b;
+}
+
+// gpu::emit_batch's `sums`: the outer UDP checksum (and the IPv4 header's) of
+// the encapsulation above, filled in the same launch, verify as a receiver
+// checks them, and nothing else differs from the call without sums.
+TEST(encapsulate_with_sums) {
+    std::vector<std::vector<uint8_t>> payloads;
+    std::vector<uint32_t> ports, vnis;
+    encap_inputs(payloads, ports, vnis);
+    {
+        const std::vector<uint8_t> hdr(kTunnelFrame, kTunnelFrame + 74);
+        const std::vector<gpu::EmitSet> sets = {
+            {14, INGOT_F_V6_PAYLOAD_LEN, INGOT_EMIT_LENGTH, -40, {}},
+            {54, INGOT_F_UDP_LENGTH, INGOT_EMIT_LENGTH, 0, {}},
+            {54, INGOT_F_UDP_SOURCE, INGOT_EMIT_U16, 0, ports},
+            {62, INGOT_F_GENEVE_VNI, INGOT_EMIT_U32, 0, vnis}};
+        auto plain = gpu::emit_batch(gpu::default_context(), hdr, sets, payloads);
+        auto pkts = gpu::emit_batch(gpu::default_context(), hdr, sets, payloads,
+                                    {{INGOT_EMIT_SUM_UDP, 54, 14}});
+        ASSERT_EQ(pkts.size(), 300u);
+        for (uint32_t i = 0; i < 300; ++i) {
+            const auto& p = pkts[i];
+            ASSERT_EQ(p.size(), 74 + payloads[i].size());
+            ASSERT_TRUE(l4_ok(p, 14, 54, ip::IpProtocol::UDP));
+            ASSERT_TRUE(p[60] != 0 || p[61] != 0);  // 0 would mean "no checksum"
+            ASSERT_TRUE(same_but(p, plain[i], {60}));
+            ASSERT_EQ((int)plain[i][60], 0);
+            ASSERT_EQ((int)plain[i][61], 0);
+        }
+    }
+    {
+        // Eth / IPv4 / UDP / Geneve (50 B), a per-packet source address
+        std::vector<uint8_t> hdr = {
+            0xA8, 0x40, 0x25, 0x77, 0x77, 0x76, 0xA8, 0x40, 0x25, 0x77, 0x77, 0x77, 0x08, 0x00,
+            0x45, 0, 0, 0, 0, 0, 0, 0, 64, 17, 0, 0, 10, 0, 0, 1, 10, 0, 0, 2,
+            0xC0, 0xDE, 0x17, 0xC1, 0, 0, 0, 0,
+            0x00, 0x00, 0x65, 0x58, 0x00, 0xAB, 0xCD, 0x00};
+        std::vector<uint32_t> addrs;
+        for (uint32_t i = 0; i < 300; ++i) addrs.push_back(0x0A000100u + i * 0x01010101u);
+        const std::vector<gpu::EmitSet> sets = {
+            {14, INGOT_F_V4_TOTAL_LEN, INGOT_EMIT_LENGTH, 0, {}},
+            {34, INGOT_F_UDP_LENGTH, INGOT_EMIT_LENGTH, 0, {}},
+            {14, INGOT_F_V4_SOURCE, INGOT_EMIT_U32, 0, addrs}};
+        auto plain = gpu::emit_batch(gpu::default_context(), hdr, sets, payloads);
+        auto pkts = gpu::emit_batch(gpu::default_context(), hdr, sets, payloads,
+                                    {{INGOT_EMIT_SUM_IPV4, 14}, {INGOT_EMIT_SUM_UDP, 34, 14}});
+        for (uint32_t i = 0; i < 300; ++i) {
+            const auto& p = pkts[i];
+            ASSERT_EQ(p.size(), 50 + payloads[i].size());
+            ASSERT_TRUE(v4_header_ok(p, 14));
+            ASSERT_TRUE(l4_ok(p, 14, 34, ip::IpProtocol::UDP));
+            ASSERT_TRUE(p[40] != 0 || p[41] != 0);
+            ASSERT_TRUE(same_but(p, plain[i], {24, 40}));
+        }
+    }
+}
+
+// gpu::modify_batch's `what`: a NAT-style rewrite (source address, destination
+// port, hop limit) of IPv4 UDP and TCP frames with valid sums leaves both sums
+// valid, and changes nothing but the checksum fields relative to what == 0.
+TEST(nat_rewrite_keeps_sums_valid) {
+    std::vector<std::vector<uint8_t>> frames;
+    for (uint32_t i = 0; i < 200; ++i) {
+        const bool tcp = i & 1;
+        std::vector<uint8_t> f = {0xA8, 0x40, 0x25, 0x77, 0x77, 0x76, 0xA8, 0x40, 0x25, 0x77,
+                                  0x77, 0x77, 0x08, 0x00,
+                                  0x45, 0, 0, 0, 0x1C, 0x46, 0x40, 0, 64, (uint8_t)(tcp ? 6 : 17),
+                                  0, 0, 192, 168, (uint8_t)(i >> 8), (uint8_t)i, 8, 8, 8, 8};
+        if (tcp)
+            f.insert(f.end(), {0xC0, (uint8_t)i, 0x01, 0xBB, 1, 2, 3, 4, 0, 0, 0, 0, 0x50, 0x18,
+                               0xFF, 0xFF, 0, 0, 0, 0});
+        else
+            f.insert(f.end(), {0x00, 0x35, 0x9C, (uint8_t)i, 0, 0, 0, 0});
+        for (uint32_t k = 0; k < i % 23; ++k) f.push_back((uint8_t)(k * 7 + i));  // odd and even
+        const size_t l4_len = f.size() - 34, field = tcp ? 50 : 40;
+        put16(f, 16, (uint16_t)(f.size() - 14));
+        if (!tcp) put16(f, 38, (uint16_t)l4_len);
+        put16(f, 24, (uint16_t)~sum1071(&f[14], 20));
+        std::vector<uint8_t> pseudo(f.begin() + 26, f.begin() + 34);
+        for (uint8_t b : {(uint8_t)0, f[23], (uint8_t)(l4_len >> 8), (uint8_t)l4_len})
+            pseudo.push_back(b);
+        uint16_t c = (uint16_t)~sum1071(&f[34], l4_len, sum1071(pseudo.data(), pseudo.size()));
+        if (!tcp && c == 0) c = 0xffff;
+        put16(f, field, c);
+        ASSERT_TRUE(v4_header_ok(f, 14));
+        ASSERT_TRUE(l4_ok(f, 14, 34, f[23]));
+        frames.push_back(f);
+    }
+    const uint8_t L3 = GenericUlp::INNER_L3_LAYER, L4 = GenericUlp::INNER_ULP_LAYER;
+    const std::vector<ingot_edit> edits = {
+        gpu::edit(L3, INGOT_F_V4_SOURCE, INGOT_OP_SET, 0x0A000001),
+        gpu::edit(L4, INGOT_F_UDP_DESTINATION, INGOT_OP_SUB, 1),
+        gpu::edit(L4, INGOT_F_TCP_DESTINATION, INGOT_OP_SET, 8443),
+        gpu::edit(L3, INGOT_F_V4_HOP_LIMIT, INGOT_OP_SUB, 1)};
+    auto plain = gpu::modify_batch(gpu::default_context(), frames, GenericUlp::CHAIN, edits, 0);
+    auto out = gpu::modify_batch(gpu::default_context(), frames, GenericUlp::CHAIN, edits,
+                                 INGOT_CSUM_L3 | INGOT_CSUM_L4);
+    ASSERT_EQ(out.size(), 200u);
+    for (uint32_t i = 0; i < 200; ++i) {
+        const auto& m = out[i];
+        const bool tcp = i & 1;
+        ASSERT_EQ((int)m.rec.status, (int)INGOT_OK);
+        ASSERT_EQ((int)m.frame[22], 63);
+        ASSERT_EQ((int)m.frame[26], 10);
+        ASSERT_TRUE(m.frame != frames[i]);
+        ASSERT_TRUE(v4_header_ok(m.frame, 14));
+        ASSERT_TRUE(l4_ok(m.frame, 14, 34, m.frame[23]));
+        ASSERT_TRUE(!v4_header_ok(plain[i].frame, 14));       // the plain rewrite left them stale
+        ASSERT_TRUE(!l4_ok(plain[i].frame, 14, 34, m.frame[23]));
+        ASSERT_TRUE(same_but(m.frame, plain[i].frame, {24, (size_t)(tcp ? 50 : 40)}));
+        ASSERT_EQ(std::memcmp(&m.rec, &plain[i].rec, sizeof(ingot_rec)), 0);
     }
 }
 
