@@ -39,7 +39,8 @@ extern "C" {
 #endif
 
 /* 4: ingot_gpu_checksum_verify / ingot_gpu_checksum_fill (ingot_csum);
- *    ingot_gpu_parse_modify_csum (an added call: the number stays).
+ *    ingot_gpu_parse_modify_csum, ingot_gpu_checksum_verify_read / _fill_read
+ *    (added calls: the number stays).
  * 3: ingot_gpu_comm_wrap (borrow the host's RCCL communicator).
  * 2: ingot_gpu_comm_* / ingot_gpu_flow_hist_allreduce (config 5's reduce);
  *    host mappings counted per map, ingot_gpu_host_unmap EINVAL for a pointer
@@ -907,7 +908,8 @@ int ingot_gpu_emit_headers(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_
  * ERANGE from the LDS-fit check as in ingot_gpu_emit_packets.
  *
  * Out of scope: sums in ingot_gpu_emit_headers (that kernel never sees the
- * payload); inner-frame checksums (ingot_gpu_checksum_fill on the source
+ * payload; the header slot and the source frame are a two-chunk packet, and
+ * ingot_gpu_checksum_fill_read fills its outer UDP sum in place); inner-frame checksums (ingot_gpu_checksum_fill on the source
  * arena before the emit); TCP and ICMP kinds.
  * ------------------------------------------------------------------------- */
 enum ingot_emit_sum_kind { INGOT_EMIT_SUM_IPV4 = 0, INGOT_EMIT_SUM_UDP = 1 };
@@ -1019,6 +1021,73 @@ int ingot_gpu_checksum_fill(ingot_gpu_ctx* ctx, uint8_t* d_arena,
                             const uint64_t* d_off, const uint16_t* d_len,
                             uint32_t stride, uint64_t n, const ingot_rec* d_rec,
                             uint32_t what, ingot_csum* d_out, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The two checksum calls over chunked packets: the chunk tables of
+ * ingot_gpu_parse_read (packet i is the chunks d_pkt_seg[i] .. d_pkt_seg[i+1]
+ * of (d_seg_off, d_seg_len), in order), driven by the 16-B records an earlier
+ * ingot_gpu_parse_read (any of its forms) wrote over the same chunks, under
+ * any chain.  For a header-split receive ring (headers in one buffer, the
+ * payload in another), for the two-chunk packet ingot_gpu_emit_headers makes
+ * (header slot + the untouched source frame: the outer UDP sum without
+ * copying the payload), and for an inner frame that arrives as a chain.
+ * Build-defined, like the contiguous pair; tests/csum_read_model.py is the
+ * definition.  `what`, the ingot_csum rows, the states and which of d_out may
+ * be NULL are those of ingot_gpu_checksum_verify / _fill.
+ *
+ * The logical frame is the chunks concatenated, cut at 65,535 bytes
+ * (parse_read: later bytes are not seen); L is its length, and
+ * d_pkt_seg[i+1] < d_pkt_seg[i] counts as no chunks (L = 0).  A packet's row
+ * is the row ingot_gpu_checksum_verify gives for that logical frame with that
+ * record, under one added rule: a header is read from one chunk.  "The span
+ * [a, b) lies in one chunk" means that some chunk k of the packet has
+ * start_k <= a and b <= start_k + len_k, start_k being the logical offset of
+ * its first byte.
+ *   - Where the contiguous definition requires l3_off + fixed <= L (fixed = 20
+ *     for IPv4, 40 for IPv6), [l3_off, l3_off + fixed) must also lie in one
+ *     chunk; otherwise the row is NONE / NONE.
+ *   - L3: where it requires l3_off + max(20, ihl * 4) <= L, that span must
+ *     also lie in one chunk; otherwise L3 is NONE.
+ *   - L4: besides the contiguous geometry test, [l3_off, l4_off) (the L3
+ *     header as parsed, IPv6 extension headers included: the fragment walk
+ *     reads them) must lie in one chunk, and so must [l4_off, payload_off)
+ *     (the L4 header as parsed); otherwise L4 is NONE.
+ * Every record ingot_gpu_parse_read itself wrote satisfies the rule (ingot
+ * parses a header from one slice); the rule decides only what a caller's own
+ * or stale records get.  The segment [l4_off, end) itself may cross any
+ * number of chunk boundaries, at odd and even offsets, through empty chunks;
+ * chunks or bytes past `end` (Ethernet padding, a trailing chunk) are not
+ * summed, and end > L is SHORT, as before.  For a GENEVE_OVER_V6 record the
+ * layers are the inner ones; the outer UDP sum of a chunked tunnel packet
+ * comes from a UDP_PARSER ingot_gpu_parse_read of the same chunks.
+ *
+ * ingot_gpu_checksum_fill_read writes exactly the two field bytes of every
+ * layer verify would call OK, BAD or ZERO (the rule puts them inside one
+ * chunk) and nothing else, neither the gaps between chunks nor a chunk's
+ * other bytes, and reports the state after writing.  Chunks of different
+ * packets may alias for verify; for fill, a chunk that holds a written field
+ * must not be shared between packets of one call.  Reads stay inside each
+ * non-empty chunk's 16-byte blocks (the contiguous calls' contract, per
+ * chunk); an empty chunk's offset is never dereferenced.
+ *
+ * All argument checks happen before any device work.  EINVAL: a NULL context;
+ * `what` 0 or with any other bit; for n > 0 a NULL d_arena, d_rec or any of
+ * the three tables; d_out NULL in verify.  n == 0 succeeds.
+ *
+ * Out of scope: the dense (offset << 16) | length table and the d_first form
+ * of parse_read; a chunked form of ingot_gpu_parse_modify or
+ * ingot_gpu_emit_packets; k_csum itself (the contiguous calls are unchanged).
+ * ------------------------------------------------------------------------- */
+int ingot_gpu_checksum_verify_read(ingot_gpu_ctx* ctx, const uint8_t* d_arena,
+                                   const uint64_t* d_seg_off, const uint16_t* d_seg_len,
+                                   const uint32_t* d_pkt_seg, uint64_t n,
+                                   const ingot_rec* d_rec, uint32_t what, ingot_csum* d_out,
+                                   void* stream);
+int ingot_gpu_checksum_fill_read(ingot_gpu_ctx* ctx, uint8_t* d_arena,
+                                 const uint64_t* d_seg_off, const uint16_t* d_seg_len,
+                                 const uint32_t* d_pkt_seg, uint64_t n,
+                                 const ingot_rec* d_rec, uint32_t what, ingot_csum* d_out,
+                                 void* stream);
 
 /* ---------------------------------------------------------------------------
  * Parse + rewrite + incremental checksum update (RFC 1624) in one launch: what

@@ -610,6 +610,47 @@ class Context:
         return self._checksum("ingot_gpu_checksum_fill", arena, off, lens, recs, what, stride,
                               n, out, stream)
 
+    def _checksum_read(self, name: str, arena, seg_off, seg_len, pkt_seg, recs, what: int, out,
+                       stream):
+        n = pkt_seg.numel() - 1
+        if int(what) == 0 or int(what) & ~(CSUM_L3 | CSUM_L4):
+            raise ValueError("what must be CSUM_L3, CSUM_L4 or both")
+        self._arg("arena", arena, _U8)
+        self._arg("pkt_seg", pkt_seg, _U32, n + 1)
+        self._arg("seg_off", seg_off, _U64)
+        self._arg("seg_len", seg_len, _U16, seg_off.numel())
+        self._arg("recs", recs, _U8, n * REC_BYTES)
+        self._arg("out", out, _U8, n * CSUM_BYTES, optional=True)
+        self._on_device(arena=arena, seg_off=seg_off, seg_len=seg_len, pkt_seg=pkt_seg,
+                        recs=recs, out=out)
+        fn = getattr(self._lib, name)
+        _lib.check(fn(self._h, _ptr(arena), _ptr(seg_off), _ptr(seg_len), _ptr(pkt_seg), n,
+                      _ptr(recs), int(what), _ptr(out), _stream(stream, self.device)), name)
+        return out
+
+    def checksum_verify_read(self, arena, seg_off, seg_len, pkt_seg, recs,
+                             what: int = CSUM_L3 | CSUM_L4, out=None, stream=None):
+        """ingot_gpu_checksum_verify_read: checksum_verify over the chunk
+        tables of parse_read (packet i = chunks pkt_seg[i]..pkt_seg[i+1] of
+        (seg_off, seg_len)), with the records parse_read wrote over the same
+        chunks.  A header is read from one chunk; the L4 segment may cross
+        any number of them.  Returns an (n, 8) uint8 tensor of ingot_csum
+        rows (CSUM_DTYPE)."""
+        if out is None:
+            out = _torch().empty((pkt_seg.numel() - 1, CSUM_BYTES), dtype=_torch().uint8,
+                                 device=arena.device)
+        return self._checksum_read("ingot_gpu_checksum_verify_read", arena, seg_off, seg_len,
+                                   pkt_seg, recs, what, out, stream)
+
+    def checksum_fill_read(self, arena, seg_off, seg_len, pkt_seg, recs,
+                           what: int = CSUM_L3 | CSUM_L4, out=None, stream=None):
+        """ingot_gpu_checksum_fill_read: compute the selected checksums of
+        chunked packets and write them into their chunks, in place (two bytes
+        per layer, nothing else).  `out` (optional, (n, 8) uint8) receives the
+        ingot_csum rows after writing; returns it (None when not given)."""
+        return self._checksum_read("ingot_gpu_checksum_fill_read", arena, seg_off, seg_len,
+                                   pkt_seg, recs, what, out, stream)
+
     def flow_hist(self, arena, off, lens, chain: Chain, hist=None, bins: Optional[int] = None,
                   stride: int = 0, n: Optional[int] = None, key: Optional[bytes] = None,
                   flow=None, hashes=None, workspace=None, stream=None):

@@ -877,9 +877,41 @@ int checksum(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off, const 
     return from_hip(ingot_gpu::launch_csum(a, (hipStream_t)stream));
 }
 
+// The two calls over parse_read's chunk tables, checked the same way.
+int checksum_read(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_seg_off,
+                  const uint16_t* d_seg_len, const uint32_t* d_pkt_seg, uint64_t n,
+                  const ingot_rec* d_rec, uint32_t what, ingot_csum* d_out, bool fill,
+                  void* stream) {
+    if (!ctx || what == 0 || (what & ~(INGOT_CSUM_L3 | INGOT_CSUM_L4))) return INGOT_GPU_EINVAL;
+    if (n == 0) return INGOT_GPU_SUCCESS;
+    if (!d_arena || !d_seg_off || !d_seg_len || !d_pkt_seg || !d_rec || (!d_out && !fill))
+        return INGOT_GPU_EINVAL;
+    if (int e = enter(ctx)) return e;
+    ingot_gpu::CsumReadArgs a{d_arena, d_seg_off, d_seg_len, d_pkt_seg, n, d_rec, d_out, what,
+                              fill ? 1u : 0u};
+    return from_hip(ingot_gpu::launch_csum_read(a, (hipStream_t)stream));
+}
+
 }  // namespace
 
 extern "C" {
+
+int ingot_gpu_checksum_verify_read(ingot_gpu_ctx* ctx, const uint8_t* d_arena,
+                                   const uint64_t* d_seg_off, const uint16_t* d_seg_len,
+                                   const uint32_t* d_pkt_seg, uint64_t n, const ingot_rec* d_rec,
+                                   uint32_t what, ingot_csum* d_out, void* stream) {
+    // the kernel writes the arena only in fill mode
+    return checksum_read(ctx, const_cast<uint8_t*>(d_arena), d_seg_off, d_seg_len, d_pkt_seg, n,
+                         d_rec, what, d_out, false, stream);
+}
+
+int ingot_gpu_checksum_fill_read(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_seg_off,
+                                 const uint16_t* d_seg_len, const uint32_t* d_pkt_seg, uint64_t n,
+                                 const ingot_rec* d_rec, uint32_t what, ingot_csum* d_out,
+                                 void* stream) {
+    return checksum_read(ctx, d_arena, d_seg_off, d_seg_len, d_pkt_seg, n, d_rec, what, d_out,
+                         true, stream);
+}
 
 int ingot_gpu_checksum_verify(ingot_gpu_ctx* ctx, const uint8_t* d_arena, const uint64_t* d_off,
                               const uint16_t* d_len, uint32_t stride, uint64_t n,

@@ -194,6 +194,22 @@ struct CsumArgs {
 };
 hipError_t launch_csum(const CsumArgs& a, hipStream_t s);
 
+// The same sums over parse_read's chunk tables (ingot_gpu_checksum_verify_read /
+// _fill_read, k_csum_read in csum.hip): packet i is the chunks pkt_seg[i] ..
+// pkt_seg[i+1] of (seg_off, seg_len).
+struct CsumReadArgs {
+    uint8_t* arena;            // written only when `fill`
+    const uint64_t* seg_off;   // per chunk
+    const uint16_t* seg_len;   // per chunk
+    const uint32_t* pkt_seg;   // n+1 chunk-index bounds
+    uint64_t n;
+    const ingot_rec* rec;
+    ingot_csum* out;           // optional when `fill`
+    uint32_t what;             // INGOT_CSUM_L3 | INGOT_CSUM_L4
+    uint32_t fill;
+};
+hipError_t launch_csum_read(const CsumReadArgs& a, hipStream_t s);
+
 // Lengths-only packed frames (packed.hip): tile base = u64 base of its group
 // of PACKED_GROUP tiles (at the start of `work`, >= packed_workspace(n)
 // bytes) + the tile's u32 prefix within the group (after the group bases).

@@ -12,10 +12,12 @@ model of tests/csum_model.py, so on at most --csum-frames frames per case),
 and the rewrite with the fused checksum update (`modify_csum`: against the
 oracle's rewrite + the Python model of tests/csum_update_model.py, same cap),
 and the emit with checksums (`emit_csum`: against the oracle's emit + the
-Python model of tests/emit_csum_model.py, same cap).
+Python model of tests/emit_csum_model.py, same cap), and the checksum calls
+over chunked packets (`csum_read`, only with --only: verify, fill, verify again
+over cut generator frames against tests/csum_read_model.py, same cap).
 
     python tools/bigfuzz.py [--frames 4000000] [--seed 1234]
-                            [--only csum|modify_csum|emit_csum]
+                            [--only csum|modify_csum|emit_csum|csum_read]
 """
 from __future__ import annotations
 
@@ -199,6 +201,75 @@ def emit_csum_cases(ctx, n, seed, res):
         torch.cuda.empty_cache()
 
 
+def csum_read_cases(ctx, n, seed, res):
+    """ingot_gpu_checksum_verify_read, then _fill_read and a second verify, over
+    generator frames cut into chunks (tests/csum_read_cases.py: header cuts at
+    layer edges, payload cuts anywhere, empty chunks, every chunk at its own
+    misalignment) with the device's own parse_read records, against the model
+    of tests/csum_read_model.py.  Every other case has its sums filled first
+    (OK rows), the others keep the generator's random sums (BAD rows)."""
+    import torch
+
+    import ingot_amd
+    from ingot_amd import CSUM_DTYPE, Chain, GenProfile
+    from tests import csum_read_cases as cases
+    from tests import csum_read_model as model
+
+    def rows(t):
+        return t.cpu().numpy().view(CSUM_DTYPE).reshape(-1)
+
+    def dev(a):
+        signed = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32,
+                  np.dtype(np.uint64): np.int64}
+        return torch.from_numpy(a.view(signed.get(a.dtype, a.dtype))).cuda()
+
+    pairs = [(GenProfile.MIXED, Chain.GenericUlp), (GenProfile.VLAN_V6EH, Chain.VlanUlp),
+             (GenProfile.GENEVE, Chain.GeneveOverV6Tunnel), (GenProfile.MIXED, Chain.UdpParser),
+             (GenProfile.ADVERSARIAL, Chain.GenericUlp)]
+    for k, (prof, chain) in enumerate(pairs):
+        arena, off, lens = ingot_amd.gen_frames(prof, n, seed=seed + 130 + k)
+        recs = ctx.parse(arena, off, lens, chain)
+        if k % 2:
+            ctx.checksum_fill(arena, off, lens, recs)
+        torch.cuda.synchronize()
+        rng = np.random.default_rng(seed + 130 + k)
+        crec = ingot_amd.records_to_numpy(recs)
+        frames = cases.frames_of(arena.cpu().numpy(), off.cpu().numpy().view(np.uint64),
+                                 lens.cpu().numpy())
+        packets = [cases.cut(f, crec[i], rng) for i, f in enumerate(frames)]
+        a, so, sl, ps = cases.place(packets, misalign=list(range(16)) + [int(rng.integers(16))],
+                                    gap=int(rng.integers(0, 4)))
+        d_a, d_tab = dev(a), (dev(so), dev(sl), dev(ps))
+        d_rec, _ = ctx.parse_read(d_a, *d_tab, chain)
+        rec = ingot_amd.records_to_numpy(d_rec)
+        got_v = rows(ctx.checksum_verify_read(d_a, *d_tab, d_rec))
+        wrote = int((d_a.cpu().numpy() != a).sum())
+        want_v = model.verify((a, so, sl, ps), rec)
+        out = torch.zeros((n, 8), dtype=torch.uint8, device="cuda")
+        ctx.checksum_fill_read(d_a, *d_tab, d_rec, out=out)
+        want_f = model.fill((a, so, sl, ps), rec)
+        got_a = rows(ctx.checksum_verify_read(d_a, *d_tab, d_rec))
+        torch.cuda.synchronize()
+        key = f"csum_read/{prof.name}/{chain.name}"
+        res[key] = {
+            "records_unlike_the_contiguous_parse": int((rec.view(np.uint8).reshape(n, -1) !=
+                                                          crec.view(np.uint8).reshape(n, -1))
+                                                         .any(axis=1).sum()),
+            "verify_row_mismatches": int((got_v.view(np.uint64) != want_v.view(np.uint64)).sum()),
+            "verify_byte_mismatches": wrote,
+            "fill_row_mismatches": int((rows(out).view(np.uint64) != want_f.view(np.uint64)).sum()),
+            "fill_byte_mismatches": int((d_a.cpu().numpy() != a).sum()),
+            "verify_after_fill_row_mismatches": int((got_a.view(np.uint64)
+                                                     != want_f.view(np.uint64)).sum()),
+            "sums_filled_first": bool(k % 2),
+            "chunks": int(ps[-1]), "chunks_per_packet_max": int(np.diff(ps.astype(np.int64)).max()),
+            "l4_states_before": np.bincount(want_v["l4_state"], minlength=6).tolist(),
+            "l4_states_after": np.bincount(want_f["l4_state"], minlength=6).tolist()}
+        print(key, res[key], flush=True)
+        del arena, off, lens, recs, out, d_a, d_tab, d_rec
+        torch.cuda.empty_cache()
+
+
 def finish(n, seed, t0, res):
     out = {"frames_per_case": n, "seed": seed, "wall_s": round(time.time() - t0, 1),
            "cases": res,
@@ -215,14 +286,15 @@ def main():
     ap.add_argument("--csum-frames", type=int, default=200_000,
                     help="frames per csum case (its reference is a Python model)")
     ap.add_argument("--only", default="",
-                    help="'csum' / 'modify_csum' / 'emit_csum': run only that case group")
+                    help="'csum' / 'modify_csum' / 'emit_csum' / 'csum_read': run only that "
+                         "case group")
     args = ap.parse_args()
-    if args.only in ("csum", "modify_csum", "emit_csum"):
+    if args.only in ("csum", "modify_csum", "emit_csum", "csum_read"):
         import ingot_amd
 
         res, t0 = {}, time.time()
         group = {"csum": csum_cases, "modify_csum": modify_csum_cases,
-                 "emit_csum": emit_csum_cases}[args.only]
+                 "emit_csum": emit_csum_cases, "csum_read": csum_read_cases}[args.only]
         group(ingot_amd.Context(0), min(args.frames, args.csum_frames), args.seed, res)
         return finish(min(args.frames, args.csum_frames), args.seed, t0, res)
 

@@ -17,7 +17,20 @@ L3 headers read (20 / 40 B) + the descriptors (10 B per packed frame, none for
 slots) + the 16-B record, 8 B written per packet.  Gather: the frames read and
 written + 18 B of descriptors per packet.
 
-    python tools/csum_probe.py [--frames N] [--reps 5] [--rounds 5] [--out F]
+With --read, the chunked calls (k_csum_read) on the C3 frames join the same
+interleaved rounds, beside c3_verify as the yardstick:
+
+  c3_read_1chunk_verify   ingot_gpu_checksum_verify_read, every packet one
+                          chunk (the like-for-like case);
+  c3_read_split_verify    header-split: two chunks cut at payload_off (the
+                          whole frame and an empty chunk where the record is
+                          not Ok), in place in the same arena;
+  c3_read_split_fill      ingot_gpu_checksum_fill_read over the same tables.
+
+Their algorithmic bytes are the checksum's with 10 B per chunk and 4 B per
+packet of tables in place of the 10 B of packed descriptors.
+
+    python tools/csum_probe.py [--frames N] [--reps 5] [--rounds 5] [--read] [--out F]
 """
 from __future__ import annotations
 
@@ -37,6 +50,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--copies", type=int, default=2, help="arenas rotated per layout")
+    ap.add_argument("--read", action="store_true",
+                    help="add the chunked calls (checksum_verify_read / _fill_read) on c3")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
 
@@ -102,6 +117,49 @@ def main():
             ctx.emit_packets(b"", [], a, go, gl, d, do)
 
         runs[f"{name}_verify"], runs[f"{name}_gather"], runs[f"{name}_fill"] = verify, gather, fill
+        if args.read and name == "c3":
+            one, two = [], []
+            for a, o, ln, rc, rw, *_ in sets:
+                ps1 = torch.arange(n + 1, dtype=torch.int32, device="cuda")
+                r1, _ = ctx.parse_read(a, o, ln, ps1, chain)
+                one.append((a, o, ln, ps1, r1, rw))
+                L = ln.to(torch.int32) & 0xFFFF
+                pay = rc[:, 12].to(torch.int32) | (rc[:, 13].to(torch.int32) << 8)
+                pay = torch.where(rc[:, 0] == 0, torch.minimum(pay, L), L)
+                so = torch.stack((o, o + pay.to(torch.int64)), dim=1).reshape(-1).contiguous()
+                sl = torch.stack((pay, L - pay), dim=1).reshape(-1).to(torch.int16).contiguous()
+                ps2 = ps1 * 2
+                r2, _ = ctx.parse_read(a, so, sl, ps2, chain)
+                two.append((a, so, sl, ps2, r2, rw))
+            ctx.checksum_verify_read(*two[0][:5], out=two[0][5])
+            torch.cuda.synchronize()
+            r2 = two[0][5].cpu().numpy().view(CSUM_DTYPE).reshape(-1)
+            meta[name]["split_rows_unlike_contiguous"] = int((r2.view("uint64") !=
+                                                              r.view("uint64")).sum())
+            meta[name]["chunks"] = {"one": n, "split": 2 * n}
+            base = seg + hdr + n * (16 + 8 + 4)
+            algo["c3_read_1chunk_verify"] = base + 10 * n
+            algo["c3_read_split_verify"] = algo["c3_read_split_fill"] = base + 20 * n
+            rturn = {"k": 0}
+
+            def rpick(which, rturn=rturn):
+                rturn["k"] += 1
+                return which[rturn["k"] % len(which)]
+
+            def read1(rpick=rpick, one=one):
+                a, so, sl, ps, rc, rw = rpick(one)
+                ctx.checksum_verify_read(a, so, sl, ps, rc, out=rw)
+
+            def read2(rpick=rpick, two=two):
+                a, so, sl, ps, rc, rw = rpick(two)
+                ctx.checksum_verify_read(a, so, sl, ps, rc, out=rw)
+
+            def fill2(rpick=rpick, two=two):
+                a, so, sl, ps, rc, rw = rpick(two)
+                ctx.checksum_fill_read(a, so, sl, ps, rc, out=rw)
+
+            runs["c3_read_1chunk_verify"], runs["c3_read_split_verify"] = read1, read2
+            runs["c3_read_split_fill"] = fill2
     for f in runs.values():  # warm up every shape (fill also makes the sums valid: same work)
         for _ in range(args.copies):
             f()
