@@ -595,6 +595,83 @@ inline std::vector<Modified> modify_batch(Context& ctx,
     return out;
 }
 
+// The same setters over chunk lists (ingot_gpu_parse_read_modify, what != 0:
+// ingot_gpu_parse_read_modify_csum): packet i = packets[i], parsed with
+// parse_read's chunk semantics and, when Ok, edited in place at the record's
+// logical offsets.  Returns every packet's chunks after the call, its record
+// and the chunk holding the remainder.
+struct ModifiedRead {
+    Chunks chunks;
+    ingot_rec rec;
+    uint16_t chunk;
+};
+
+inline std::vector<ModifiedRead> modify_read_batch(Context& ctx,
+                                                   const std::vector<Chunks>& packets, int chain,
+                                                   const std::vector<ingot_edit>& edits,
+                                                   uint32_t what = 0) {
+    const size_t n = packets.size();
+    std::vector<uint64_t> seg_off;
+    std::vector<uint16_t> seg_len;
+    std::vector<uint32_t> pkt_seg{0};
+    std::vector<uint8_t> arena;
+    for (const auto& chunks : packets) {
+        for (const auto& c : chunks) {
+            if (c.size() > 65535) throw std::length_error("chunk longer than 65535 bytes");
+            seg_off.push_back(arena.size());
+            seg_len.push_back((uint16_t)c.size());
+            arena.insert(arena.end(), c.begin(), c.end());
+            arena.resize((arena.size() + 15) / 16 * 16 + 16, 0);  // chunks apart in memory
+        }
+        pkt_seg.push_back((uint32_t)seg_off.size());
+    }
+    seg_off.push_back(arena.size());  // keeps the tables non-empty
+    seg_len.push_back(0);
+    arena.resize(arena.size() + 64, 0);
+    uint8_t* d_arena = nullptr;
+    uint64_t* d_off = nullptr;
+    uint16_t *d_len = nullptr, *d_chunk = nullptr;
+    uint32_t* d_ps = nullptr;
+    ingot_rec* d_rec = nullptr;
+    hip_check(hipMalloc(&d_arena, arena.size()), "hipMalloc");
+    hip_check(hipMalloc(&d_off, seg_off.size() * 8), "hipMalloc");
+    hip_check(hipMalloc(&d_len, seg_len.size() * 2), "hipMalloc");
+    hip_check(hipMalloc(&d_ps, pkt_seg.size() * 4), "hipMalloc");
+    hip_check(hipMalloc(&d_rec, n * sizeof(ingot_rec) + 16), "hipMalloc");
+    hip_check(hipMalloc(&d_chunk, n * 2 + 8), "hipMalloc");
+    hip_check(hipMemcpy(d_arena, arena.data(), arena.size(), hipMemcpyHostToDevice), "H2D");
+    hip_check(hipMemcpy(d_off, seg_off.data(), seg_off.size() * 8, hipMemcpyHostToDevice), "H2D");
+    hip_check(hipMemcpy(d_len, seg_len.data(), seg_len.size() * 2, hipMemcpyHostToDevice), "H2D");
+    hip_check(hipMemcpy(d_ps, pkt_seg.data(), pkt_seg.size() * 4, hipMemcpyHostToDevice), "H2D");
+    if (what)
+        check(ingot_gpu_parse_read_modify_csum(ctx.get(), d_arena, d_off, d_len, d_ps, n, chain,
+                                               edits.data(), (uint32_t)edits.size(), what, d_rec,
+                                               d_chunk, nullptr),
+              "ingot_gpu_parse_read_modify_csum");
+    else
+        check(ingot_gpu_parse_read_modify(ctx.get(), d_arena, d_off, d_len, d_ps, n, chain,
+                                          edits.data(), (uint32_t)edits.size(), d_rec, d_chunk,
+                                          nullptr),
+              "ingot_gpu_parse_read_modify");
+    std::vector<ingot_rec> rec(n);
+    std::vector<uint16_t> chunk(n);
+    hip_check(hipMemcpy(arena.data(), d_arena, arena.size(), hipMemcpyDeviceToHost), "D2H");
+    hip_check(hipMemcpy(rec.data(), d_rec, n * sizeof(ingot_rec), hipMemcpyDeviceToHost), "D2H");
+    hip_check(hipMemcpy(chunk.data(), d_chunk, n * 2, hipMemcpyDeviceToHost), "D2H");
+    std::vector<ModifiedRead> out(n);
+    for (size_t i = 0; i < n; ++i) {
+        for (uint32_t k = pkt_seg[i]; k < pkt_seg[i + 1]; ++k)
+            out[i].chunks.emplace_back(arena.begin() + (long)seg_off[k],
+                                       arena.begin() + (long)(seg_off[k] + seg_len[k]));
+        out[i].rec = rec[i];
+        out[i].chunk = chunk[i];
+    }
+    for (void* p : {(void*)d_arena, (void*)d_off, (void*)d_len, (void*)d_ps, (void*)d_rec,
+                    (void*)d_chunk})
+        (void)hipFree(p);
+    return out;
+}
+
 // Batched Emit (ingot_gpu_emit_packets): `hdr` = an owned header stack
 // emitted once (ingot's emit_vec on the host), the setters applied per packet
 // (values per packet for INGOT_EMIT_U16 / U32 sources), then each payload.

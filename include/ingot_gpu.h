@@ -39,7 +39,8 @@ extern "C" {
 #endif
 
 /* 4: ingot_gpu_checksum_verify / ingot_gpu_checksum_fill (ingot_csum);
- *    ingot_gpu_parse_modify_csum, ingot_gpu_checksum_verify_read / _fill_read
+ *    ingot_gpu_parse_modify_csum, ingot_gpu_checksum_verify_read / _fill_read,
+ *    ingot_gpu_parse_read_modify / ingot_gpu_parse_read_modify_csum
  *    (added calls: the number stays).
  * 3: ingot_gpu_comm_wrap (borrow the host's RCCL communicator).
  * 2: ingot_gpu_comm_* / ingot_gpu_flow_hist_allreduce (config 5's reduce);
@@ -1075,8 +1076,8 @@ int ingot_gpu_checksum_fill(ingot_gpu_ctx* ctx, uint8_t* d_arena,
  * the three tables; d_out NULL in verify.  n == 0 succeeds.
  *
  * Out of scope: the dense (offset << 16) | length table and the d_first form
- * of parse_read; a chunked form of ingot_gpu_parse_modify or
- * ingot_gpu_emit_packets; k_csum itself (the contiguous calls are unchanged).
+ * of parse_read; a chunked form of ingot_gpu_emit_packets; k_csum itself
+ * (the contiguous calls are unchanged).
  * ------------------------------------------------------------------------- */
 int ingot_gpu_checksum_verify_read(ingot_gpu_ctx* ctx, const uint8_t* d_arena,
                                    const uint64_t* d_seg_off, const uint16_t* d_seg_len,
@@ -1138,6 +1139,66 @@ int ingot_gpu_parse_modify_csum(ingot_gpu_ctx* ctx, uint8_t* d_arena,
                                 uint32_t stride, uint64_t n, int chain,
                                 const ingot_edit* edits, uint32_t n_edits,
                                 uint32_t what, ingot_rec* d_out, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The rewrite over chunked packets: ingot_gpu_parse_read, then ingot's setters
+ * in place over the chunk lists, and (_csum) the RFC 1624 update of the
+ * selected sums in the same launch.  For packets held as an mblk chain or in
+ * a header-split ring, and for the two-chunk packet ingot_gpu_emit_headers
+ * makes (header slot + the untouched source frame): hop limit, NAT of an
+ * address or a port, a VNI, with the sums kept right and no payload byte
+ * read or copied.  tests/modify_read_model.py is the definition.
+ *
+ * Tables and records.  (d_seg_off, d_seg_len, d_pkt_seg) are the CSR tables of
+ * ingot_gpu_parse_read.  d_out and d_chunk are both optional; whatever is
+ * written to them is byte for byte what ingot_gpu_parse_read writes for the
+ * same tables and bytes: the parse sees the bytes before the edits.
+ *
+ * Where edits land.  Only packets whose record is Ok are edited; every other
+ * packet (StraddledHeader, TooSmall, no chunks, ...) has no byte written.  For
+ * an Ok packet the edits are ingot_gpu_parse_modify's, in order: the same
+ * layer / field / kind matching, ops wrapping modulo 2^width, neighbouring
+ * bits preserved, raw wire values; a later edit sees what the earlier ones
+ * wrote.  Offsets come from this one parse and are the record's logical
+ * offsets (the chunks concatenated): the tunnel chain's outer offsets from
+ * the walk, VLAN tag `index` at 14 + 4 * index.  Logical byte x of a packet
+ * lives in the chunk k with start_k <= x < start_k + len_k, start_k the sum of
+ * the earlier chunks' lengths; an empty chunk holds no byte and its offset is
+ * never dereferenced.  Every header parse_read accepted lies in one chunk, so
+ * each edited field and each checksum field lies in one chunk.
+ *
+ * Checksum update.  `what`, the sums, their covered bytes, the EINVAL rules
+ * and the refused fields are ingot_gpu_parse_modify_csum's.  Its "even frame
+ * offsets" are even logical offsets: a byte's place in its 16-bit word is the
+ * parity of its logical offset, whatever the chunk's address.  Inner sums come
+ * first, then OUTER_L4 (tunnel chain only).
+ *
+ * Bytes written: exactly the covering bytes of each applied edit and the two
+ * bytes of each updated checksum field, each stored as a byte.  Gaps between
+ * chunks, other packets' chunks and payload chunks are not stored to at all.
+ *
+ * Aliasing: a chunk that holds a header the call may write must not be shared
+ * between packets of one call; chunks that are only parsed past (payload) may.
+ *
+ * All argument checks happen before any device work: ingot_gpu_parse_modify's
+ * (_csum: and ingot_gpu_parse_modify_csum's) own, then n == 0 succeeds, then
+ * for n > 0 a NULL d_arena or any NULL table is EINVAL.  Results never depend
+ * on tuning knobs; INGOT_TUNE_READ_PLAN 1 is honoured as in
+ * ingot_gpu_parse_read (17 means 0).
+ *
+ * Out of scope: the dense table and the d_first / lazy forms of parse_read.
+ * ------------------------------------------------------------------------- */
+int ingot_gpu_parse_read_modify(ingot_gpu_ctx* ctx, uint8_t* d_arena,
+                                const uint64_t* d_seg_off, const uint16_t* d_seg_len,
+                                const uint32_t* d_pkt_seg, uint64_t n, int chain,
+                                const ingot_edit* edits, uint32_t n_edits,
+                                ingot_rec* d_out, uint16_t* d_chunk, void* stream);
+int ingot_gpu_parse_read_modify_csum(ingot_gpu_ctx* ctx, uint8_t* d_arena,
+                                     const uint64_t* d_seg_off, const uint16_t* d_seg_len,
+                                     const uint32_t* d_pkt_seg, uint64_t n, int chain,
+                                     const ingot_edit* edits, uint32_t n_edits,
+                                     uint32_t what, ingot_rec* d_out, uint16_t* d_chunk,
+                                     void* stream);
 
 /*
  * Flow classification + per-flow histogram (config 5; build-defined, ingot

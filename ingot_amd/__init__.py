@@ -504,6 +504,38 @@ class Context:
             "ingot_gpu_parse_modify")
         return out
 
+    def parse_read_modify(self, arena, seg_off, seg_len, pkt_seg, chain: Chain, edits,
+                          csum: int = 0, out=None, chunk=None, stream=None):
+        """parse_read, then ingot's setters in place over the chunk lists
+        (ingot_gpu_parse_read_modify): the tables are parse_read's, `edits`
+        parse_modify's, applied in order at the record's logical offsets to
+        packets that parse Ok.  `out` ((n, 16) uint8) and `chunk` (n, int16)
+        are optional and get what parse_read would write; returns (out, chunk).
+
+        csum != 0 (CSUM_L3 | CSUM_L4 | CSUM_OUTER_L4): the same launch also
+        updates those checksums from the bytes the edits changed (RFC 1624,
+        ingot_gpu_parse_read_modify_csum)."""
+        n = pkt_seg.numel() - 1
+        self._arg("arena", arena, _U8)
+        self._arg("pkt_seg", pkt_seg, _U32, n + 1)
+        self._arg("seg_off", seg_off, _U64)
+        self._arg("seg_len", seg_len, _U16, seg_off.numel())
+        self._arg("out", out, _U8, n * REC_BYTES, optional=True)
+        self._arg("chunk", chunk, _U16, n, optional=True)
+        e = edits_array(edits)
+        self._on_device(arena=arena, seg_off=seg_off, seg_len=seg_len, pkt_seg=pkt_seg, out=out,
+                        chunk=chunk)
+        args = (self._h, _ptr(arena), _ptr(seg_off), _ptr(seg_len), _ptr(pkt_seg), n, int(chain),
+                e.ctypes.data_as(ctypes.c_void_p), len(e))
+        tail = (_ptr(out), _ptr(chunk), _stream(stream, self.device))
+        if int(csum):
+            _lib.check(self._lib.ingot_gpu_parse_read_modify_csum(*args, int(csum), *tail),
+                       "ingot_gpu_parse_read_modify_csum")
+        else:
+            _lib.check(self._lib.ingot_gpu_parse_read_modify(*args, *tail),
+                       "ingot_gpu_parse_read_modify")
+        return out, chunk
+
     def _emit_sets(self, sets, n: int):
         """[(at, Field, EmitSource, add[, per-packet cuda tensor]), ...] ->
         (ingot_emit_set array, tensors kept alive for the call)."""

@@ -639,14 +639,15 @@ int csum_feeds(int chain, const ingot_edit& e, uint32_t what) {
     return (int)f;
 }
 
-// ingot_gpu_parse_modify (what == 0) and ingot_gpu_parse_modify_csum: every
-// argument is checked before any device work.
-int modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off, const uint16_t* d_len,
-           uint32_t stride, uint64_t n, int chain, const ingot_edit* edits, uint32_t n_edits,
-           uint32_t what, ingot_rec* d_out, void* stream) {
+// The edit list of a rewrite call -> the kernels' argument block (shared by
+// the contiguous and the chunked rewrites): each ingot_edit's field resolved
+// to its header kind and BE bit geometry and, with `what`, to the sums its
+// bytes feed.  The checks run in this order: NULL context, chain, the list's
+// size, unknown field / op / layer, refused fields.
+int resolve_edits(const ingot_gpu_ctx* ctx, int chain, const ingot_edit* edits, uint32_t n_edits,
+                  uint32_t what, ingot_gpu::ModifyCsumArgs& c) {
     if (!ctx || !chain_ok(chain) || n_edits > INGOT_MAX_EDITS || (n_edits && !edits))
         return INGOT_GPU_EINVAL;
-    ingot_gpu::ModifyCsumArgs c{};  // (the checksum update's extras: used when what != 0)
     ingot_gpu::ModifyArgs& a = c.m;
     c.what = what;
     for (uint32_t k = 0; k < n_edits; ++k) {
@@ -672,6 +673,24 @@ int modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off, const ui
         }
     }
     a.n_edits = n_edits;
+    return INGOT_GPU_SUCCESS;
+}
+
+// ingot_gpu_parse_modify_csum's and ingot_gpu_parse_read_modify_csum's `what`.
+bool csum_what_ok(uint32_t what, int chain) {
+    const uint32_t all = INGOT_CSUM_L3 | INGOT_CSUM_L4 | INGOT_CSUM_OUTER_L4;
+    return what != 0 && !(what & ~all) &&
+           (!(what & INGOT_CSUM_OUTER_L4) || chain == INGOT_CHAIN_GENEVE_OVER_V6);
+}
+
+// ingot_gpu_parse_modify (what == 0) and ingot_gpu_parse_modify_csum: every
+// argument is checked before any device work.
+int modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off, const uint16_t* d_len,
+           uint32_t stride, uint64_t n, int chain, const ingot_edit* edits, uint32_t n_edits,
+           uint32_t what, ingot_rec* d_out, void* stream) {
+    ingot_gpu::ModifyCsumArgs c{};  // (the checksum update's extras: used when what != 0)
+    ingot_gpu::ModifyArgs& a = c.m;
+    if (int e = resolve_edits(ctx, chain, edits, n_edits, what, c)) return e;
     if (n == 0) return INGOT_GPU_SUCCESS;
     if (!d_arena) return INGOT_GPU_EINVAL;
     int layout = ingot_gpu::LAYOUT_INDEXED;
@@ -686,6 +705,23 @@ int modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off, const ui
     const ingot_gpu::Tuning t = tuning_for(ctx, d_arena);
     return from_hip(what ? ingot_gpu::launch_modify_csum(c, layout, chain, t, (hipStream_t)stream)
                          : ingot_gpu::launch_modify(a, layout, chain, t, (hipStream_t)stream));
+}
+
+// ingot_gpu_parse_read_modify (what == 0) and ingot_gpu_parse_read_modify_csum:
+// the same edit list over parse_read's CSR chunk tables.
+int read_modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_seg_off,
+                const uint16_t* d_seg_len, const uint32_t* d_pkt_seg, uint64_t n, int chain,
+                const ingot_edit* edits, uint32_t n_edits, uint32_t what, ingot_rec* d_out,
+                uint16_t* d_chunk, void* stream) {
+    ingot_gpu::ModifyCsumArgs c{};
+    if (int e = resolve_edits(ctx, chain, edits, n_edits, what, c)) return e;
+    if (n == 0) return INGOT_GPU_SUCCESS;
+    if (!d_arena || !d_seg_off || !d_seg_len || !d_pkt_seg) return INGOT_GPU_EINVAL;
+    if (int e = enter(ctx)) return e;
+    c.m.p = ingot_gpu::ParseArgs{d_arena, d_seg_off, d_seg_len, 0, n, d_out, d_pkt_seg, d_chunk};
+    const ingot_gpu::Tuning t = tuning_for(ctx, d_arena);
+    return from_hip(what ? ingot_gpu::launch_read_modify_csum(c, chain, t, (hipStream_t)stream)
+                         : ingot_gpu::launch_read_modify(c.m, chain, t, (hipStream_t)stream));
 }
 
 }  // namespace
@@ -704,12 +740,27 @@ int ingot_gpu_parse_modify_csum(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint
                                 const uint16_t* d_len, uint32_t stride, uint64_t n, int chain,
                                 const ingot_edit* edits, uint32_t n_edits, uint32_t what,
                                 ingot_rec* d_out, void* stream) {
-    const uint32_t all = INGOT_CSUM_L3 | INGOT_CSUM_L4 | INGOT_CSUM_OUTER_L4;
-    if (what == 0 || (what & ~all) ||
-        ((what & INGOT_CSUM_OUTER_L4) && chain != INGOT_CHAIN_GENEVE_OVER_V6))
-        return INGOT_GPU_EINVAL;
+    if (!csum_what_ok(what, chain)) return INGOT_GPU_EINVAL;
     return modify(ctx, d_arena, d_off, d_len, stride, n, chain, edits, n_edits, what, d_out,
                   stream);
+}
+
+int ingot_gpu_parse_read_modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_seg_off,
+                                const uint16_t* d_seg_len, const uint32_t* d_pkt_seg, uint64_t n,
+                                int chain, const ingot_edit* edits, uint32_t n_edits,
+                                ingot_rec* d_out, uint16_t* d_chunk, void* stream) {
+    return read_modify(ctx, d_arena, d_seg_off, d_seg_len, d_pkt_seg, n, chain, edits, n_edits,
+                       0u, d_out, d_chunk, stream);
+}
+
+int ingot_gpu_parse_read_modify_csum(ingot_gpu_ctx* ctx, uint8_t* d_arena,
+                                     const uint64_t* d_seg_off, const uint16_t* d_seg_len,
+                                     const uint32_t* d_pkt_seg, uint64_t n, int chain,
+                                     const ingot_edit* edits, uint32_t n_edits, uint32_t what,
+                                     ingot_rec* d_out, uint16_t* d_chunk, void* stream) {
+    if (!csum_what_ok(what, chain)) return INGOT_GPU_EINVAL;
+    return read_modify(ctx, d_arena, d_seg_off, d_seg_len, d_pkt_seg, n, chain, edits, n_edits,
+                       what, d_out, d_chunk, stream);
 }
 
 }  // extern "C"

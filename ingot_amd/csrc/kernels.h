@@ -270,6 +270,12 @@ hipError_t launch_modify_ring_csum(const ModifyCsumArgs& a, int chain, const Tun
                                    hipStream_t s);
 hipError_t launch_modify_csum(const ModifyCsumArgs& a, int layout_kind, int chain,
                               const Tuning& t, hipStream_t s);
+// The rewrite over parse_read's chunk tables (ingot_gpu_parse_read_modify[_csum],
+// read.hip): `a.p` holds the CSR tables as LAYOUT_SEGMENTED does, out and chunk
+// both optional.
+hipError_t launch_read_modify(const ModifyArgs& a, int chain, const Tuning& t, hipStream_t s);
+hipError_t launch_read_modify_csum(const ModifyCsumArgs& a, int chain, const Tuning& t,
+                                   hipStream_t s);
 bool tuning_valid(int key, int value);
 
 }  // namespace ingot_gpu

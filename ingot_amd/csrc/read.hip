@@ -1,6 +1,8 @@
 // read.hip — parse_read over chunk lists (ingot_gpu_parse_read*,
 // ingot-macros/src/parse.rs:511-537): the k_parse_read kernel with the header
-// chunks staged in LDS (SegFrameP) and its launcher; DESIGN.md §1b.
+// chunks staged in LDS (SegFrameP) and its launcher; DESIGN.md §1b.  And the
+// rewrite over chunk lists (ingot_gpu_parse_read_modify*): k_parse_read_modify
+// and its launchers; DESIGN.md §4.11.
 #include "walk.h"
 
 namespace ingot_gpu {
@@ -222,6 +224,239 @@ __global__ __launch_bounds__(BLOCK) void k_parse_read(ParseArgs a) {
     }
 }
 
+// The rewrite over chunk lists: the frame view the shared setters and checksum
+// update (walk.h: apply_edit, csum_finish — unchanged, one copy) read through
+// after the walk, and where their bytes go.
+// Offsets are the record's logical offsets (the chunks concatenated); logical
+// byte x lies in the chunk k with start_k <= x < start_k + len_k, start_k the
+// sum of the earlier chunks' lengths (an empty chunk holds no byte and its
+// offset is never used).  The chunk is found by walking the lengths from the
+// one found last — chunks 0..3 from the walk's registers (1..3 only when not
+// the packet's last, as prefetched), later ones from the table, never past the
+// packet's last chunk — and from chunk 0 again when x lies before it.
+// Every byte is read from and stored to global memory, so an edit sees what
+// the earlier edits of its packet wrote; nothing is staged or written back in
+// wider units, so no byte outside an edited field or checksum field is stored
+// to.  A header parse_read accepted lies in one chunk; bytes that would
+// reach past the chunk found (never the case for an Ok record) read as 0 and
+// are not stored.
+template <class SF>
+struct ChunkView {
+    const SF& f;  // the walk's view, after the walk
+    mutable uint32_t ck = 0, cstart = 0, clen;
+    mutable uint64_t coff;
+    __device__ __forceinline__ explicit ChunkView(const SF& s) : f(s), clen(s.l0), coff(s.o0) {}
+
+    // the chunk holding logical bytes [x, x + n); false: none does
+    __device__ __forceinline__ bool locate(uint32_t x, uint32_t n) const {
+        if (x < cstart) {
+            ck = 0;
+            cstart = 0;
+            clen = f.l0;
+            coff = f.o0;
+        }
+        while (x - cstart >= clen) {
+            if (ck + 1u >= f.nseg) return false;
+            cstart += clen;
+            ++ck;
+            const bool pre = ck + 1u < f.nseg;  // a prefetched descriptor is valid
+            if (pre && ck == 1u) {
+                coff = f.o1;
+                clen = f.l1;
+            } else if (pre && ck == 2u) {
+                coff = f.o2;
+                clen = f.l2;
+            } else if (pre && ck == 3u) {
+                coff = f.o3;
+                clen = f.l3;
+            } else {
+                coff = gbl(f.seg_off)[f.s0 + ck];
+                clen = gbl(f.seg_len)[f.s0 + ck];
+            }
+        }
+        return x - cstart + n <= clen;
+    }
+    __device__ __forceinline__ uint32_t be(uint32_t i, uint32_t n) const {
+        uint32_t v = 0;
+        if (locate(i, n)) {
+            const auto* gg = gbl(f.arena) + coff + (i - cstart);
+            for (uint32_t j = 0; j < n; ++j) v = (v << 8) | gg[j];
+        }
+        return v;
+    }
+    __device__ __forceinline__ uint32_t be_edited(uint32_t i, uint32_t n) const { return be(i, n); }
+    __device__ __forceinline__ uint32_t get_edited(uint32_t hdr, Field fl) const {
+        return (be(hdr + fl.byte0(), fl.nbytes()) >> fl.rshift()) & fl.mask();
+    }
+};
+
+// The edit sink of a chunked packet: walk.h's put_byte for this view (the more
+// specialised overload, found by the shared apply_edit through its frame
+// argument).  One byte store into the chunk that holds the byte; the
+// EditSink, the contiguous kernels' write-back bookkeeping, is not used.
+template <class SF>
+__device__ __forceinline__ void put_byte(const ChunkView<SF>& f, EditSink&, uint32_t i,
+                                         uint8_t v) {
+    if (f.locate(i, 1u))
+        gbl_mut(const_cast<uint8_t*>(f.f.arena))[f.coff + (i - f.cstart)] = v;
+}
+
+// The rewrite over chunk lists (ingot_gpu_parse_read_modify, ARGS = ModifyArgs;
+// ingot_gpu_parse_read_modify_csum, ARGS = ModifyCsumArgs): k_parse_read's
+// record path over the CSR tables (three prefetched descriptors, the window
+// from byte 12), then ingot's setters at the record's logical offsets and,
+// with ModifyCsumArgs, the RFC 1624 update of the selected sums.
+//
+// The staging is k_parse_read's, line for line, in a kernel of its own: a
+// body shared through a helper (tried both with the LDS image declared in the
+// kernels and in the helper) gave five of k_parse_read's dense-table kernels
+// other registers, and those kernels keep the instructions they were measured
+// with.
+//
+// After the walk nothing is read from the LDS image again.  The setters and
+// the checksum update read and store the few bytes they touch in global
+// memory through ChunkView (above) — the lines are in L2 from the staging —
+// so an edit sees what earlier edits of the packet wrote (a field edited
+// twice, a checksum field set by an edit and then updated), and every store
+// is a byte store inside the one chunk that holds the header: no neighbouring
+// byte, which may belong to a packet another lane is editing, is written.
+template <int CS0, int CHAIN, class ARGS>
+__global__ __launch_bounds__(BLOCK) void k_parse_read_modify(ARGS args) {
+    constexpr bool CSUM = std::is_same<ARGS, ModifyCsumArgs>::value;
+    const ParseArgs& a = base_args(args);
+    using FR = SegFrameP<CS0, false, 3, false>;
+    constexpr uint32_t WAVE_DW = WAVE * CS0 * 4u;
+    __shared__ __attribute__((aligned(16))) uint32_t s_win[WAVES * WAVE_DW];
+    const uint32_t lane = threadIdx.x & (WAVE - 1u);
+    const uint32_t wave = threadIdx.x / WAVE;
+    uint32_t* wimg = s_win + wave * WAVE_DW;
+    const uint64_t ntiles = (a.n + WAVE - 1u) / WAVE;
+    const uint64_t W = (uint64_t)gridDim.x * WAVES;
+
+    for (uint64_t t = (uint64_t)blockIdx.x * WAVES + wave; t < ntiles; t += W) {
+        const uint64_t i = t * WAVE + lane;
+        const bool valid = i < a.n;
+        // the packet's chunk bounds (clamped index) and descriptors 0..3
+        // (1..3 only when not the packet's last: SegFrameP::advance)
+        const uint64_t ic = valid ? i : a.n - 1u;
+        const uint32_t b0 = a.pkt_seg[ic], b1 = a.pkt_seg[ic + 1];
+        const uint32_t s0 = valid ? b0 : 0u;
+        const uint32_t nseg = valid && b1 > b0 ? b1 - b0 : 0u;
+        FR fr;
+        fr.o0 = nseg ? a.off[s0] : 0u;
+        fr.l0 = nseg ? a.len[s0] : 0u;
+        fr.o1 = nseg > 2 ? a.off[s0 + 1] : 0u;
+        fr.o2 = nseg > 3 ? a.off[s0 + 2] : 0u;
+        fr.o3 = nseg > 4 ? a.off[s0 + 3] : 0u;
+        fr.l1 = nseg > 2 ? a.len[s0 + 1] : 0u;
+        fr.l2 = nseg > 3 ? a.len[s0 + 2] : 0u;
+        fr.l3 = nseg > 4 ? a.len[s0 + 3] : 0u;
+        // chunk 0's window from the piece holding its byte SKIP, packet-major
+        // (k_parse_read's staging)
+        constexpr uint32_t SKIP = INGOT_REC_SKIP;
+        const uint32_t sh0 = (uint32_t)((uintptr_t)(a.arena + fr.o0 + SKIP) & 15u);
+        const int64_t base0 = (int64_t)fr.o0 + (int64_t)SKIP - (int64_t)sh0;
+        uint32_t want = CS0;
+        if (a.linewin) {
+            const uint32_t lp = (uint32_t)((uintptr_t)(a.arena + base0) >> 4) & 7u;
+            want = ((lp + a.linewin + 7u) & ~7u) - lp;
+            if (want > (uint32_t)CS0) want = CS0;
+        }
+        const uint32_t wlim = 16u * want;
+        const int64_t e0 = (int64_t)sh0 + (int64_t)fr.l0 - (int64_t)SKIP;
+        uint32_t ext = nseg && e0 > 0 ? (e0 < (int64_t)wlim ? (uint32_t)e0 : wlim) : 0u;
+        auto widen = [&](uint32_t e, uint64_t o, uint32_t l) {
+            const int64_t d = (int64_t)o - base0;
+            if (e + 1 < nseg && d >= 0 && d < (int64_t)wlim) {
+                const uint32_t end = (uint32_t)d + l < wlim ? (uint32_t)d + l : wlim;
+                ext = end > ext ? end : ext;
+            }
+        };
+        widen(1, fr.o1, fr.l1);
+        widen(2, fr.o2, fr.l2);
+        widen(3, fr.o3, fr.l3);
+        const uint32_t n0 = (ext + 15u) >> 4;
+#pragma unroll
+        for (uint32_t k = 0; k < (uint32_t)CS0; ++k) {
+            const auto [pp, c] = chunk_of<CS0>(k, lane);
+            const uint32_t np = (uint32_t)__shfl((int)n0, (int)pp);
+            const int64_t bp = (int64_t)__shfl((long long)base0, (int)pp);
+            if (c < np) stage16(a.arena + bp + 16u * c, wimg + k * WAVE * 4u, false);
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+
+        fr.win = (const lds_u32*)wimg;
+        fr.p = lane;
+        fr.arena = a.arena;
+        fr.seg_off = a.off;
+        fr.seg_len = a.len;
+        fr.s0 = s0;
+        fr.k = 0;
+        fr.nseg = nseg;
+        fr.pkt_seg = a.pkt_seg;
+        fr.pi = i;
+        fr.L = 0;
+        fr.b0 = base0;
+        fr.span0 = 16u * n0;
+        fr.enter(fr.o0, fr.l0, nseg ? want : 0u);
+        fr.sh = sh0 - SKIP;
+        const uint32_t w0 = 16u * want + SKIP - sh0;
+        fr.avail = nseg ? (fr.l0 < w0 ? fr.l0 : w0) : 0u;
+
+        Rec r;
+        walk<CHAIN, false>(fr, r, nullptr, nullptr);
+        // the image is not read below: the next tile's LDS-DMA may overwrite
+        // it once every lane's reads above have returned
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        if (valid && a.out) store_rec(static_cast<uint4*>(a.out) + i, pack(r), a.policy);
+        if (valid && a.chunk) a.chunk[i] = (uint16_t)fr.k;
+        // the setters, in order, on packets parsed Ok (no store for any
+        // other packet, nor for lanes past n)
+        if (valid && r.status == INGOT_OK) {
+            const ChunkView<FR> cv(fr);
+            EditSink sink{};  // (unused by this view's put_byte)
+            [[maybe_unused]] typename std::conditional<CSUM, CsumAcc, NoCsum>::type acc;
+            const ModifyArgs& m = edit_args(args);
+            for (uint32_t k = 0; k < m.n_edits; ++k) {
+                const Edit e = m.e[k];
+                uint32_t h;
+                if (header_at<CHAIN>(r, e.layer, e.kind, e.index, h)) {
+                    if constexpr (CSUM)
+                        csum_feed(acc, args.feeds[k], r, apply_edit<true>(cv, sink, h, e));
+                    else
+                        apply_edit(cv, sink, h, e);
+                }
+            }
+            if constexpr (CSUM)
+                csum_finish<CHAIN>(cv, r, args.what, acc,
+                                   [&](uint32_t at, uint8_t v) { put_byte(cv, sink, at, v); });
+        }
+    }
+}
+
+// The rewrite's launcher: parse_read's chunk-0 window (launch_segmented below:
+// INGOT_TUNE_READ_PLAN 1, or an arena in mapped host memory, = 4 pieces; else
+// the line-completing 3 to 5), its record stores and its grid.
+template <class ARGS>
+hipError_t launch_read_modify_as(const ARGS& args, int chain, const Tuning& t, hipStream_t s) {
+    ARGS b = args;
+    ParseArgs& p = edit_args(b).p;
+    if (p.n == 0) return hipSuccess;
+    p.policy = t.cache_policy == 0 ? 2u : (uint32_t)t.cache_policy & 0x1fbu;  // launch_parse's
+    const uint32_t g = grid_for(p.n, t.max_blocks);
+    const bool four = t.read_plan == 1 || (t.read_plan == 0 && t.host_arena);
+    if (!four) p.linewin = 3u;
+    with_chain<INGOT_CHAIN_GENEVE_OVER_V6>(chain, [&](auto c) {
+        if (four)
+            hipLaunchKernelGGL((k_parse_read_modify<4, decltype(c)::value, ARGS>), dim3(g),
+                               dim3(BLOCK), 0, s, b);
+        else
+            hipLaunchKernelGGL((k_parse_read_modify<5, decltype(c)::value, ARGS>), dim3(g),
+                               dim3(BLOCK), 0, s, b);
+    });
+    return hipGetLastError();
+}
+
 template <int CS0, int MODE, bool DENSE = false, int NPRE = 3, bool FIRST = false,
           bool LAZY = false>
 hipError_t launch_read(const ParseArgs& a, int chain, uint32_t g, hipStream_t s) {
@@ -234,6 +469,15 @@ hipError_t launch_read(const ParseArgs& a, int chain, uint32_t g, hipStream_t s)
 }
 
 }  // namespace
+
+hipError_t launch_read_modify(const ModifyArgs& a, int chain, const Tuning& t, hipStream_t s) {
+    return launch_read_modify_as(a, chain, t, s);
+}
+
+hipError_t launch_read_modify_csum(const ModifyCsumArgs& a, int chain, const Tuning& t,
+                                   hipStream_t s) {
+    return launch_read_modify_as(a, chain, t, s);
+}
 
 // parse_read over chunk lists.  Measured (tools/abtune.py, us per launch,
 // DESIGN.md §1b): the reference's one-header-per-chunk shape (c2r, 1 M) 33.3

@@ -14,10 +14,12 @@ oracle's rewrite + the Python model of tests/csum_update_model.py, same cap),
 and the emit with checksums (`emit_csum`: against the oracle's emit + the
 Python model of tests/emit_csum_model.py, same cap), and the checksum calls
 over chunked packets (`csum_read`, only with --only: verify, fill, verify again
-over cut generator frames against tests/csum_read_model.py, same cap).
+over cut generator frames against tests/csum_read_model.py, same cap), and the
+rewrite over chunked packets (`modify_read`, only with --only: random edit
+lists over cut generator frames against tests/modify_read_model.py, same cap).
 
     python tools/bigfuzz.py [--frames 4000000] [--seed 1234]
-                            [--only csum|modify_csum|emit_csum|csum_read]
+                            [--only csum|modify_csum|emit_csum|csum_read|modify_read]
 """
 from __future__ import annotations
 
@@ -270,6 +272,70 @@ def csum_read_cases(ctx, n, seed, res):
         torch.cuda.empty_cache()
 
 
+def modify_read_cases(ctx, n, seed, res):
+    """ingot_gpu_parse_read_modify / _csum over csum_read's generator profiles x
+    chains, cut by tests/csum_read_cases.py's `cut`, with random edit lists of
+    tests/csum_sweep_cases.py (and every `what` of the chain in turn, 0
+    included), against tests/modify_read_model.py: the whole arena, the
+    records and the chunk indices.  Every other case has its sums filled
+    first."""
+    import torch
+
+    import ingot_amd
+    from ingot_amd import Chain, GenProfile
+    from tests import csum_read_cases as cases
+    from tests import csum_sweep_cases as sc
+    from tests import modify_read_model as model
+
+    def dev(a):
+        signed = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32,
+                  np.dtype(np.uint64): np.int64}
+        return torch.from_numpy(a.view(signed.get(a.dtype, a.dtype))).cuda()
+
+    pairs = [(GenProfile.MIXED, Chain.GenericUlp), (GenProfile.VLAN_V6EH, Chain.VlanUlp),
+             (GenProfile.GENEVE, Chain.GeneveOverV6Tunnel), (GenProfile.MIXED, Chain.UdpParser),
+             (GenProfile.ADVERSARIAL, Chain.GenericUlp)]
+    for k, (prof, chain) in enumerate(pairs):
+        arena, off, lens = ingot_amd.gen_frames(prof, n, seed=seed + 160 + k)
+        recs = ctx.parse(arena, off, lens, chain)
+        if k % 2:
+            ctx.checksum_fill(arena, off, lens, recs)
+        torch.cuda.synchronize()
+        rng = np.random.default_rng(seed + 160 + k)
+        crec = ingot_amd.records_to_numpy(recs)
+        frames = cases.frames_of(arena.cpu().numpy(), off.cpu().numpy().view(np.uint64),
+                                 lens.cpu().numpy())
+        packets = [cases.cut(f, crec[i], rng) for i, f in enumerate(frames)]
+        tables = cases.place(packets, misalign=list(range(16)) + [int(rng.integers(16))],
+                             gap=int(rng.integers(0, 4)))
+        parsed = model.parse(tables, chain)
+        pristine, d_tab = dev(tables[0]), [dev(x) for x in tables[1:]]
+        out = torch.zeros((n, 16), dtype=torch.uint8, device="cuda")
+        chunk = torch.zeros(n, dtype=torch.int16, device="cuda")
+        whats = (0,) + tuple(sc.WHATS[chain])
+        lists = sc.random_lists(chain, 6, seed=seed + k)
+        bytes_bad = recs_bad = chunk_bad = edited = 0
+        for j, edits in enumerate(lists):
+            what = whats[j % len(whats)]
+            want, w_rec, w_chunk = model.apply(tables, chain, edits, what, parsed=parsed)
+            d_a = pristine.clone()
+            ctx.parse_read_modify(d_a, *d_tab, chain, edits, csum=what, out=out, chunk=chunk)
+            got = d_a.cpu().numpy()
+            bytes_bad += int((got != want).sum())
+            recs_bad += int((out.cpu().numpy() != w_rec.view(np.uint8).reshape(n, 16))
+                            .any(axis=1).sum())
+            chunk_bad += int((chunk.cpu().numpy().view(np.uint16) != w_chunk).sum())
+            edited += int((want != tables[0]).sum())
+        key = f"modify_read/{prof.name}/{chain.name}"
+        res[key] = {"byte_mismatches": bytes_bad, "record_mismatches": recs_bad,
+                    "chunk_mismatches": chunk_bad, "edit_lists": len(lists),
+                    "bytes_edited": edited, "ok_packets": int((parsed[0]["status"] == 0).sum()),
+                    "chunks": int(tables[3][-1]), "sums_filled_first": bool(k % 2)}
+        print(key, res[key], flush=True)
+        del arena, off, lens, recs, out, chunk, pristine, d_tab
+        torch.cuda.empty_cache()
+
+
 def finish(n, seed, t0, res):
     out = {"frames_per_case": n, "seed": seed, "wall_s": round(time.time() - t0, 1),
            "cases": res,
@@ -286,15 +352,16 @@ def main():
     ap.add_argument("--csum-frames", type=int, default=200_000,
                     help="frames per csum case (its reference is a Python model)")
     ap.add_argument("--only", default="",
-                    help="'csum' / 'modify_csum' / 'emit_csum' / 'csum_read': run only that "
-                         "case group")
+                    help="'csum' / 'modify_csum' / 'emit_csum' / 'csum_read' / 'modify_read': "
+                         "run only that case group")
     args = ap.parse_args()
-    if args.only in ("csum", "modify_csum", "emit_csum", "csum_read"):
+    if args.only in ("csum", "modify_csum", "emit_csum", "csum_read", "modify_read"):
         import ingot_amd
 
         res, t0 = {}, time.time()
         group = {"csum": csum_cases, "modify_csum": modify_csum_cases,
-                 "emit_csum": emit_csum_cases, "csum_read": csum_read_cases}[args.only]
+                 "emit_csum": emit_csum_cases, "csum_read": csum_read_cases,
+                 "modify_read": modify_read_cases}[args.only]
         group(ingot_amd.Context(0), min(args.frames, args.csum_frames), args.seed, res)
         return finish(min(args.frames, args.csum_frames), args.seed, t0, res)
 

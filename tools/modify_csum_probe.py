@@ -28,6 +28,20 @@ under the same conditions.
 
     python tools/modify_csum_probe.py default default@plain parentA parentB \
         [--rounds 3] [--out F]
+
+With --read, the rewrite over chunked packets instead (one child process, the
+in-tree library, all rows interleaved in it): the c3nat frames cut in place at
+payload_off (header-split: two chunks per packet) with the same edit list,
+
+  a  ingot_gpu_parse_read on those tables (the floor: the new call parses the
+     same way before it edits);
+  b  ingot_gpu_parse_modify_csum, L3 | L4, on the same frames uncut;
+  c  ingot_gpu_parse_read_modify on the tables;
+  d  ingot_gpu_parse_read_modify_csum, L3 | L4, on the tables;
+
+each row's min - max of the rounds and its ratios to (a) and (b).
+
+    python tools/modify_csum_probe.py --read [--inner-rounds 5] [--out F]
 """
 from __future__ import annotations
 
@@ -119,6 +133,81 @@ def child(spec: str, n: int, reps: int, rounds: int, copies: int) -> dict:
     return {"variant": spec, "fused": fused, "us": res}
 
 
+def child_read(n: int, reps: int, rounds: int, copies: int) -> dict:
+    import torch  # before the library: one HIP runtime per process (ingot_amd/_lib.py)
+
+    import ingot_amd
+    from ingot_amd import CSUM_L3, CSUM_L4, Chain, EditOp, Field, GenProfile
+
+    ctx = ingot_amd.Context(0)
+    s = torch.cuda.current_stream()
+    what = CSUM_L3 | CSUM_L4
+    chain = Chain.GenericUlp
+    edits = [(1, Field.V4_DESTINATION, EditOp.XOR, 0x00FF00FF),
+             (2, Field.UDP_DESTINATION, EditOp.SUB, 1), (2, Field.TCP_DESTINATION, EditOp.SUB, 1),
+             (1, Field.V4_HOP_LIMIT, EditOp.SUB, 1)]
+    sets = []
+    for c in range(copies):
+        arena, off, lens = ingot_amd.gen_frames(GenProfile.MIXED, n, seed=ingot_amd.GEN_SEED + c)
+        recs = ctx.parse(arena, off, lens, chain)
+        ctx.checksum_fill(arena, off, lens, recs, n=n)  # valid sums
+        L = lens.to(torch.int32) & 0xFFFF
+        pay = recs[:, 12].to(torch.int32) | (recs[:, 13].to(torch.int32) << 8)
+        pay = torch.where(recs[:, 0] == 0, torch.minimum(pay, L), L)
+        so = torch.stack((off, off + pay.to(torch.int64)), dim=1).reshape(-1).contiguous()
+        sl = torch.stack((pay, L - pay), dim=1).reshape(-1).to(torch.int16).contiguous()
+        ps = torch.arange(n + 1, dtype=torch.int32, device="cuda") * 2
+        out = torch.empty((n, 16), dtype=torch.uint8, device="cuda")
+        chunk = torch.empty(n, dtype=torch.int16, device="cuda")
+        sets.append((arena, off, lens, so, sl, ps, out, chunk))
+    turn = {"k": 0}
+
+    def pick():
+        turn["k"] += 1
+        return sets[turn["k"] % len(sets)]
+
+    def a():
+        ar, _, _, so, sl, ps, out, ch = pick()
+        ctx.parse_read(ar, so, sl, ps, chain, out=out, chunk=ch)
+
+    def b():
+        ar, o, ln, *_ = pick()
+        ctx.parse_modify(ar, o, ln, chain, edits, n=n, csum=what)
+
+    def c():
+        ar, _, _, so, sl, ps, out, ch = pick()
+        ctx.parse_read_modify(ar, so, sl, ps, chain, edits, out=out, chunk=ch)
+
+    def d():
+        ar, _, _, so, sl, ps, out, ch = pick()
+        ctx.parse_read_modify(ar, so, sl, ps, chain, edits, csum=what, out=out, chunk=ch)
+
+    runs = {"a_parse_read": a, "b_parse_modify_csum_uncut": b, "c_parse_read_modify": c,
+            "d_parse_read_modify_csum": d}
+    for f in runs.values():
+        for _ in range(copies):
+            f()
+    torch.cuda.synchronize()
+    res = {k: [] for k in runs}
+    for _ in range(rounds):
+        for k, f in runs.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(s)
+            for _ in range(reps):
+                f()
+            e1.record(s)
+            torch.cuda.synchronize()
+            res[k].append(round(e0.elapsed_time(e1) * 1e3 / reps, 1))
+    med = {k: statistics.median(v) for k, v in res.items()}
+    rows = {k: {"min_us": min(v), "max_us": max(v), "median_us": round(med[k], 1), "rounds": v,
+                "over_a": round(med[k] / med["a_parse_read"], 3),
+                "over_b": round(med[k] / med["b_parse_modify_csum_uncut"], 3)}
+            for k, v in res.items()}
+    return {"what": "the rewrite over chunked packets: C3 frames cut at payload_off, NAT edits",
+            "frames": n, "chunks": 2 * n, "reps": reps, "copies": copies,
+            "unit": "us per call, interleaved rounds in one process", "runs": rows}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("variants", nargs="*", default=["default"])
@@ -129,7 +218,27 @@ def main():
     ap.add_argument("--copies", type=int, default=2, help="arenas rotated per layout")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--read", action="store_true",
+                    help="the rewrite over chunked packets (parse_read_modify) instead")
+    ap.add_argument("--child-read", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.child_read:
+        print(json.dumps(child_read(args.frames, args.reps, args.inner_rounds, args.copies)),
+              flush=True)
+        return
+    if args.read:
+        p = subprocess.run(
+            [sys.executable, __file__, "--child-read", "--frames", str(args.frames), "--reps",
+             str(args.reps), "--inner-rounds", str(args.inner_rounds), "--copies",
+             str(args.copies)], capture_output=True, text=True, timeout=600)
+        if p.returncode != 0:
+            raise SystemExit(f"child failed ({p.returncode}):\n{p.stdout}\n{p.stderr}")
+        out = json.loads(p.stdout.strip().splitlines()[-1])
+        print(json.dumps(out), flush=True)
+        if args.out:
+            Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.out).write_text(json.dumps(out, indent=1) + "\n")
+        return
     if args.child is not None:
         print(json.dumps(child(args.child, args.frames, args.reps, args.inner_rounds,
                                args.copies)), flush=True)
