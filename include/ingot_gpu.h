@@ -936,6 +936,66 @@ int ingot_gpu_emit_packets_csum(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t
                                 const uint64_t* d_dst_off, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Emit over chunked packets: ingot_gpu_emit_packets_csum whose source packets
+ * are the chunk lists of ingot_gpu_parse_read (an mblk chain, a header-split
+ * ring, an ingot_gpu_emit_headers slot in front of its frame).  One launch
+ * pulls the chunks up into a contiguous frame (msgpullup), puts the header
+ * block in front of it (encapsulation) or cuts the inner frame out of it
+ * (decapsulation), and fills the outer sums.  Build-defined;
+ * tests/emit_read_model.py is the definition.
+ *
+ * Payload.  The tables are those of ingot_gpu_parse_read: packet i is the
+ * chunks d_pkt_seg[i] .. d_pkt_seg[i+1] of (d_seg_off, d_seg_len), in order,
+ * at d_src + d_seg_off[k]; d_pkt_seg[i+1] < d_pkt_seg[i] counts as no chunks.
+ * The logical frame is the chunks concatenated and cut at 65,535 bytes (the
+ * rule of parse_read and of the _read checksum calls); L is its length.  With
+ * f = min(d_from[i], L) and t = min(d_take[i], L - f) (d_from NULL: 0; d_take
+ * NULL: L - f), the payload P_i is the logical bytes [f, f + t), and
+ * d_taken[i] = t when d_taken is given.  A record's payload_off, or a
+ * tunnel's inner Ethernet offset, goes straight into d_from: that is the
+ * decapsulation of a chunked tunnel packet.
+ *
+ * Output.  The bytes written are exactly those ingot_gpu_emit_packets_csum
+ * writes with the same hdr, sets, sums and d_dst_off when its source is a
+ * linear copy of P_i and d_len[i] = t: the header block, then P_i; the setters
+ * in order, INGOT_EMIT_LENGTH counting hdr_len + t; the IPV4 sum before the
+ * UDP sum; a UDP result of 0 written as 0xffff; S > 65,535 leaves the field as
+ * emitted.  n_sums == 0 is the plain emit, and with hdr_len == 0 the plain
+ * pull-up.  Nothing outside [d_dst + d_dst_off[i], + hdr_len + t) is stored
+ * to, and every destination byte is stored once (the two checksum-field bytes
+ * included: the block that holds them leaves after the sum is known).
+ *
+ * Reads.  Source reads stay inside the aligned 16-B blocks of non-empty chunks
+ * that hold a byte of P_i (the arena must be readable to the 16-B boundaries
+ * around each such chunk); an empty chunk's offset is never dereferenced; the
+ * chunk descriptors of the packet may all be read.  Source chunks may alias
+ * between packets (one payload chunk emitted behind many header chunks).
+ * Source and destination must not overlap; destination packets must not
+ * overlap.  A packet may have any number of chunks; only the first few are
+ * fast.
+ *
+ * EINVAL: ctx NULL; then ingot_gpu_emit_packets's and
+ * ingot_gpu_emit_packets_csum's own checks of hdr, sets and sums, unchanged;
+ * then, for n > 0, any of d_src, d_seg_off, d_seg_len, d_pkt_seg, d_dst,
+ * d_dst_off NULL.  n == 0 succeeds whatever the device pointers are.  ERANGE
+ * from the LDS-fit check as in ingot_gpu_emit_packets.  All of it before any
+ * device work.
+ *
+ * Out of scope: scattering the output into chunks (the destination is
+ * contiguous); the dense (offset << 16) | length table and d_first; chunk
+ * pools in mapped host memory; TCP / ICMP sum kinds and inner-frame sums
+ * (ingot_gpu_checksum_fill_read on the source chunks first).
+ * ------------------------------------------------------------------------- */
+int ingot_gpu_emit_packets_read(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
+                                const ingot_emit_set* sets, uint32_t n_sets,
+                                const ingot_emit_sum* sums, uint32_t n_sums,
+                                const uint8_t* d_src, const uint64_t* d_seg_off,
+                                const uint16_t* d_seg_len, const uint32_t* d_pkt_seg,
+                                const uint16_t* d_from, const uint16_t* d_take, uint64_t n,
+                                uint8_t* d_dst, const uint64_t* d_dst_off, uint16_t* d_taken,
+                                void* stream);
+
+/* ---------------------------------------------------------------------------
  * Internet checksums (RFC 1071) of already parsed frames: verify or fill the
  * IPv4 header checksum and the TCP / UDP / ICMPv4 / ICMPv6 checksum of every
  * packet of a batch, on the device.  Build-defined, like the flow hash: ingot
@@ -1076,8 +1136,8 @@ int ingot_gpu_checksum_fill(ingot_gpu_ctx* ctx, uint8_t* d_arena,
  * the three tables; d_out NULL in verify.  n == 0 succeeds.
  *
  * Out of scope: the dense (offset << 16) | length table and the d_first form
- * of parse_read; a chunked form of ingot_gpu_emit_packets; k_csum itself
- * (the contiguous calls are unchanged).
+ * of parse_read; k_csum itself (the contiguous calls are unchanged).  The
+ * chunked emit is ingot_gpu_emit_packets_read.
  * ------------------------------------------------------------------------- */
 int ingot_gpu_checksum_verify_read(ingot_gpu_ctx* ctx, const uint8_t* d_arena,
                                    const uint64_t* d_seg_off, const uint16_t* d_seg_len,

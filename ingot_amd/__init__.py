@@ -585,6 +585,39 @@ class Context:
             _stream(stream, self.device)), "ingot_gpu_emit_packets")
         return dst
 
+    def emit_packets_read(self, hdr: bytes, sets, src, seg_off, seg_len, pkt_seg, dst, dst_off,
+                          frm=None, take=None, taken=None, sums=(), stream=None):
+        """ingot_gpu_emit_packets_read: emit_packets whose source packets are
+        the chunk lists of parse_read (packet i = chunks pkt_seg[i] ..
+        pkt_seg[i+1] of (seg_off, seg_len) in `src`).  The payload of packet i
+        is the logical bytes [frm[i], frm[i] + take[i]) of its chunks, clamped
+        to the frame (frm=None: from byte 0; take=None: to the end); `taken`
+        (optional, n uint16) receives the bytes actually written.  hdr, sets
+        and sums as in emit_packets; sums=() is the plain emit, and with
+        hdr=b"" the plain pull-up.  Returns dst."""
+        n = pkt_seg.numel() - 1
+        hdr = bytes(hdr)
+        self._arg("src", src, _U8)
+        self._arg("pkt_seg", pkt_seg, _U32, n + 1)
+        self._arg("seg_off", seg_off, _U64)
+        self._arg("seg_len", seg_len, _U16, seg_off.numel())
+        self._arg("dst", dst, _U8)
+        self._arg("dst_off", dst_off, _U64, n)
+        self._arg("frm", frm, _U16, n, optional=True)
+        self._arg("take", take, _U16, n, optional=True)
+        self._arg("taken", taken, _U16, n, optional=True)
+        self._on_device(src=src, seg_off=seg_off, seg_len=seg_len, pkt_seg=pkt_seg, dst=dst,
+                        dst_off=dst_off, frm=frm, take=take, taken=taken)
+        s, keep = self._emit_sets(sets, n)
+        cs = emit_sums_array(sums or ())
+        h = (ctypes.c_uint8 * max(len(hdr), 1)).from_buffer_copy(hdr or b"\0")
+        _lib.check(self._lib.ingot_gpu_emit_packets_read(
+            self._h, ctypes.addressof(h), len(hdr), s.ctypes.data_as(ctypes.c_void_p), len(s),
+            cs.ctypes.data_as(ctypes.c_void_p), len(cs), _ptr(src), _ptr(seg_off), _ptr(seg_len),
+            _ptr(pkt_seg), _ptr(frm), _ptr(take), n, _ptr(dst), _ptr(dst_off), _ptr(taken),
+            _stream(stream, self.device)), "ingot_gpu_emit_packets_read")
+        return dst
+
     def emit_header_blocks(self, hdr: bytes, sets, lens, out, out_off=None, stride: int = 0,
                            stream=None):
         """ingot_gpu_emit_headers: only the header blocks, packet i's at

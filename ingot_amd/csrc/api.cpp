@@ -886,6 +886,35 @@ int ingot_gpu_emit_packets_csum(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t
                         d_dst, d_dst_off, stream);
 }
 
+int ingot_gpu_emit_packets_read(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
+                                const ingot_emit_set* sets, uint32_t n_sets,
+                                const ingot_emit_sum* sums, uint32_t n_sums, const uint8_t* d_src,
+                                const uint64_t* d_seg_off, const uint16_t* d_seg_len,
+                                const uint32_t* d_pkt_seg, const uint16_t* d_from,
+                                const uint16_t* d_take, uint64_t n, uint8_t* d_dst,
+                                const uint64_t* d_dst_off, uint16_t* d_taken, void* stream) {
+    if (!ctx) return INGOT_GPU_EINVAL;
+    ingot_gpu::EmitReadArgs a{};
+    if (int e = emit_args(hdr, hdr_len, sets, n_sets, a.e)) return e;
+    if (int e = emit_sums(hdr, hdr_len, sets, n_sets, sums, n_sums, a.e)) return e;
+    if (n == 0) return INGOT_GPU_SUCCESS;
+    if (!d_src || !d_seg_off || !d_seg_len || !d_pkt_seg || !d_dst || !d_dst_off)
+        return INGOT_GPU_EINVAL;
+    if (int e = enter(ctx)) return e;
+    a.e.src = d_src;
+    a.e.dst = d_dst;
+    a.e.dst_off = d_dst_off;
+    a.e.n = n;
+    a.seg_off = d_seg_off;
+    a.seg_len = d_seg_len;
+    a.pkt_seg = d_pkt_seg;
+    a.from = d_from;
+    a.take = d_take;
+    a.taken = d_taken;
+    if (ingot_gpu::emit_read_lds_bytes(a) > ctx->lds_bytes) return INGOT_GPU_ERANGE;
+    return from_hip(ingot_gpu::launch_emit_read(a, (hipStream_t)stream));
+}
+
 int ingot_gpu_emit_headers(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
                            const ingot_emit_set* sets, uint32_t n_sets, const uint16_t* d_len,
                            uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,

@@ -1,0 +1,470 @@
+// emit_read.hip — batched Emit over chunked packets (ingot_gpu_emit_packets_read):
+// pull-up, encapsulation and the outer checksums in one launch.
+//
+// The source of packet i is the chunk list of ingot_gpu_parse_read, cut at
+// 65,535 logical bytes, of which the bytes [f, f + t) are the payload (d_from /
+// d_take, clamped).  The destination side is k_emit's (emit.hip): the header
+// block patched per packet in an LDS region at the destination's 16-B
+// alignment, the group's packets as one flat run of aligned 16-B destination
+// blocks that the group's 16 waves take in turns, whole blocks stored whole,
+// the two edge blocks of a packet as predicated pieces (store_edge), the UDP
+// sum accumulated from the finished blocks in destination coordinates and the
+// block(s) holding its field parked until the group's barrier.
+//
+// What differs is where a block's payload bytes come from.  A *piece* is the
+// part of one non-empty chunk that lies inside the payload; in payload
+// coordinates (byte x of the payload is logical byte f + x) piece p is
+// [start_p, end_p) and its bytes sit at address sbase_p + x.  The prologue
+// lane of a packet walks the chunk lengths once (L, t, the chunk that holds f)
+// and leaves the first PIECES pieces in LDS; a block that needs a later piece
+// walks the chunk table in global memory from where the LDS table stops, with
+// a cursor that only moves forward (a block's bytes are taken in order).  A
+// block whose payload bytes lie in one piece is k_emit's load: the aligned
+// 16-B source block and its neighbour (the next lane's when that lane loaded
+// exactly that block, a second load otherwise), funnel-shifted by the piece's
+// source-vs-destination misalignment.  A block that holds a chunk boundary
+// does the same per piece and keeps each piece's bytes under a byte mask.
+// Source reads stay inside the aligned 16-B blocks that hold a byte of a
+// piece; an empty chunk's offset is never turned into an address.
+#include "emit_common.h"
+
+namespace ingot_gpu {
+namespace {
+
+constexpr uint32_t W = 16;          // waves per group (k_emit<copy>'s shape)
+constexpr uint32_t PW = 4;          // 64-packet subgroups, one prologue wave each
+constexpr uint32_t NP = PW * WAVE;  // packets per group
+constexpr uint32_t BLOCK = W * WAVE;
+constexpr uint32_t NPOW = 256;      // search span
+static_assert(NP == NPOW, "the prefix search spans the group");
+// 64-block steps whose loads fly together.  2 keeps both instantiations at or
+// under 64 VGPRs (two 1,024-thread groups per CU, as k_emit); 4 takes 81 / 91
+// and leaves room for one.
+#ifndef INGOT_EMIT_READ_UNROLL
+#define INGOT_EMIT_READ_UNROLL 2
+#endif
+constexpr uint32_t UNROLL = INGOT_EMIT_READ_UNROLL;
+constexpr uint32_t PIECES = 4;                       // pieces per packet kept in LDS
+
+// Per-group LDS.  start[k][j], k < PIECES: the payload offset at which piece k
+// of packet j starts (0xffffffff: no such piece); start[PIECES][j]: where the
+// tabled pieces end (t when they are all of them).
+struct ReadDesc {
+    uint64_t dst[NP];            // destination address of packet j
+    uint64_t sbase[PIECES][NP];  // address of payload byte 0 as piece k would have it
+    uint32_t start[PIECES + 1][NP];
+    uint32_t pfx[NP];            // inclusive prefix of block counts
+    uint32_t len[NP];            // t: payload bytes
+    uint32_t dmis[NP];           // destination address & 15
+    uint32_t cur[NP];            // first chunk index after the tabled pieces
+    uint32_t s1[NP];             // the packet's chunk bound
+    uint32_t sub[4];             // blocks of each 64-packet subgroup
+    uint32_t _pad[WAVE - 4];
+};
+
+constexpr uint32_t SUM_LDS_PER_PACKET = 4u + 2u * 16u;  // as k_emit: accumulator + two parked blocks
+
+struct Piece {
+    uint64_t sbase;
+    uint32_t start, end;
+    bool ok;
+};
+
+// The piece that holds payload byte x < t of packet q.  (s, xs) is the lane's
+// cursor into the chunk table past the LDS entries: chunk s starts at payload
+// offset xs.
+__device__ __forceinline__ Piece piece_at(const ReadDesc& wd, const EmitReadArgs& ar, uint32_t q,
+                                          uint32_t x, uint32_t t, uint32_t& s, uint32_t& xs) {
+    Piece p;
+    if (x < wd.start[PIECES][q]) {
+        uint32_t k = 0;
+#pragma unroll
+        for (uint32_t m = 1; m < PIECES; ++m) k += wd.start[m][q] <= x ? 1u : 0u;
+        p.start = wd.start[k][q];
+        p.end = min(wd.start[k + 1][q], t);
+        p.sbase = wd.sbase[k][q];
+        p.ok = true;
+        return p;
+    }
+    const uint32_t s1 = wd.s1[q];
+    uint32_t ln = 0;
+    while (s < s1) {
+        ln = gbl(ar.seg_len)[s];
+        if (xs + ln > x) break;
+        xs += ln;
+        ++s;
+    }
+    p.ok = s < s1;
+    p.start = xs;
+    p.end = min(xs + ln, t);
+    p.sbase = p.ok ? (uint64_t)(uintptr_t)ar.e.src + gbl(ar.seg_off)[s] - xs : 0u;
+    return p;
+}
+
+// The 16 bytes at X (any alignment) of piece p, zero outside the aligned
+// blocks that hold a byte of the piece.
+__device__ __forceinline__ u32x4 piece_block(const Piece& p, uint64_t X) {
+    const uint64_t B = X & ~(uint64_t)15, S0 = p.sbase + p.start, S1 = p.sbase + p.end;
+    const uint32_t sh = (uint32_t)X & 15u;
+    u32x4 lo = u32x4{0u, 0u, 0u, 0u}, hi = u32x4{0u, 0u, 0u, 0u};
+    if (B + 16 > S0 && B < S1) lo = *(const __attribute__((address_space(1))) u32x4*)B;
+    if (sh != 0 && B + 16 < S1 && B + 32 > S0)
+        hi = *(const __attribute__((address_space(1))) u32x4*)(B + 16);
+    return funnel(lo, hi, sh);
+}
+
+template <bool SUMS>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_emit_read(EmitReadArgs ar) {
+    const EmitArgs& a = ar.e;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    // the header block between zero bytes, as 16-B blocks
+    u32x4* tmpl = reinterpret_cast<u32x4*>(smem);
+    constexpr uint32_t TB = INGOT_MAX_EMIT_HDR / 16 + 4;  // 16 B before, 48 B after
+    for (uint32_t k = threadIdx.x; k < TB; k += BLOCK) {
+        const bool in = k >= 1 && k <= INGOT_MAX_EMIT_HDR / 16;
+        tmpl[k] = in ? u32x4{a.hdr[4 * k - 4], a.hdr[4 * k - 3], a.hdr[4 * k - 2],
+                             a.hdr[4 * k - 1]}
+                     : u32x4{0u, 0u, 0u, 0u};
+    }
+    const uint32_t H = a.hdr_len;
+    const uint32_t RS = region_bytes(H);
+    const uint32_t lane = threadIdx.x % WAVE;
+    const uint32_t wg = threadIdx.x / WAVE;  // this wave's turn in the group
+    ReadDesc& wd = *reinterpret_cast<ReadDesc*>(smem + TB * 16);
+    uint8_t* regions = smem + TB * 16 + sizeof(ReadDesc);
+    // SUMS: after the regions, the parked blocks, then the accumulators
+    u32x4* park = reinterpret_cast<u32x4*>(smem + TB * 16 + sizeof(ReadDesc) + NP * RS);
+    uint32_t* acc = reinterpret_cast<uint32_t*>(park + 2u * NP);
+    const bool udp = SUMS && a.sums.udp;
+    const uint32_t fpos = (uint32_t)a.sums.udp_at + 6u;  // the UDP checksum field in hdr
+    __syncthreads();
+    const uint64_t base = (uint64_t)blockIdx.x * NP;
+    if (wg < PW) {
+        // 1. wave wg, lane j: packet base + 64 wg + j.  Its chunk bounds, from /
+        //    take and destination; one walk of its chunk lengths gives L (cut
+        //    at 65,535), t, and the first PIECES pieces from the chunk that
+        //    holds logical byte `from` on
+        const uint32_t j = wg * WAVE + lane;
+        const uint64_t i = base + j;
+        const bool live = i < a.n;
+        uint32_t s0 = 0, s1 = 0;
+        if (live) {
+            s0 = gbl(ar.pkt_seg)[i];
+            s1 = gbl(ar.pkt_seg)[i + 1];
+            s1 = s1 < s0 ? s0 : s1;  // reversed bounds: no chunks
+        }
+        const uint32_t fr = (live && ar.from) ? (uint32_t)gbl(ar.from)[i] : 0u;
+        const uint32_t tk = (live && ar.take) ? (uint32_t)gbl(ar.take)[i] : 0xffffu;
+        const uint64_t doff = live ? gbl(a.dst_off)[i] : 0u;
+#pragma unroll
+        for (uint32_t k = 0; k <= PIECES; ++k) wd.start[k][j] = 0xffffffffu;
+        uint32_t g = 0, cnt = 0, cur = s1, tabled_end = 0;
+        for (uint32_t s = s0; s < s1 && g < 65535u; ++s) {
+            const uint32_t ln = min((uint32_t)gbl(ar.seg_len)[s], 65535u - g);
+            if (ln != 0 && g + ln > fr && cnt < PIECES) {
+                wd.start[cnt][j] = g > fr ? g - fr : 0u;
+                wd.sbase[cnt][j] = (uint64_t)(uintptr_t)a.src + gbl(ar.seg_off)[s] + fr - g;
+                if (++cnt == PIECES) {
+                    cur = s + 1;
+                    tabled_end = g + ln - fr;
+                }
+            }
+            g += ln;
+        }
+        const uint32_t f = min(fr, g);
+        const uint32_t L = min(tk, g - f);  // t: the payload bytes of this packet
+        wd.start[PIECES][j] = cnt == PIECES ? min(tabled_end, L) : L;
+        if (live && ar.taken) ar.taken[i] = (uint16_t)L;
+        uint32_t v[INGOT_MAX_EMIT_SETS];
+#pragma unroll
+        for (uint32_t s = 0; s < INGOT_MAX_EMIT_SETS; ++s)
+            v[s] = (s < a.n_sets && live) ? set_value(a.sets[s], i, H + L) : 0u;
+        uint8_t* D = a.dst + doff;
+        const uint32_t T = H + L;
+        const uint32_t dmis = (uint32_t)((uintptr_t)D & 15u);
+        const uint32_t nch = live ? (dmis + T + 15u) / 16u : 0u;
+
+        // 2. the packet's header block in its region, as k_emit's step 2:
+        //    template bytes shifted to the destination's alignment (region byte
+        //    b = header byte b - dmis), then the setters byte by byte
+        uint8_t* R = regions + j * RS;
+        if (H && live) {
+            for (uint32_t m = 0; m < RS / 16u; ++m) {
+                const uint32_t tb = 16u + 16u * m - dmis;
+                reinterpret_cast<u32x4*>(R)[m] = funnel(tmpl[tb >> 4], tmpl[(tb >> 4) + 1], tb & 15u);
+            }
+#pragma unroll
+            for (uint32_t s = 0; s < INGOT_MAX_EMIT_SETS; ++s) {
+                if (s >= a.n_sets) break;
+                const EmitSet& e = a.sets[s];
+                const uint32_t fm = e.bits >= 32 ? 0xffffffffu : ((1u << e.bits) - 1u);
+                const uint32_t m = fm << e.rshift, vb = (v[s] & fm) << e.rshift;
+                for (uint32_t k = 0; k < e.nbytes; ++k) {
+                    const uint32_t shb = 8u * (e.nbytes - 1u - k);
+                    uint8_t& b = R[dmis + e.pos + k];
+                    b = (uint8_t)((b & ~(m >> shb)) | ((vb >> shb) & (m >> shb)));
+                }
+            }
+        }
+
+        if constexpr (SUMS) {
+            // 2b. as k_emit's step 2b.  IPv4: complete, written into the region
+            //     before anything reads it.  UDP: the header bytes of the
+            //     segment without the field, and the pseudo-header, start the
+            //     packet's accumulator; the walkers add the payload.  All of it
+            //     has the parity of the destination address.
+            const uint32_t odd = dmis & 1u;
+            if (live && a.sums.v4) {
+                const uint32_t b0 = dmis + a.sums.v4_at;
+                R[b0 + 10] = 0;
+                R[b0 + 11] = 0;
+                const uint32_t fs = fold16(region_words(R, b0, b0 + a.sums.v4_len));
+                const uint32_t c = ~(odd ? fs : swap16(fs)) & 0xffffu;
+                R[b0 + 10] = (uint8_t)(c >> 8);
+                R[b0 + 11] = (uint8_t)c;
+            }
+            if (a.sums.udp) {
+                uint32_t s = 0;
+                if (live) {
+                    const uint32_t b0 = dmis + a.sums.udp_at, l3 = dmis + a.sums.udp_l3;
+                    const uint32_t seg = H + L - a.sums.udp_at;  // > 65535: never written
+                    const uint32_t tail = fold16(seg + 17u);     // length and next header / protocol
+                    s = region_words(R, b0, dmis + H) - ((uint32_t)R[b0 + 6] << (8u * odd)) -
+                        ((uint32_t)R[b0 + 7] << (8u * (odd ^ 1u))) +
+                        (a.sums.udp_v6 ? region_words(R, l3 + 8u, l3 + 40u)
+                                       : region_words(R, l3 + 12u, l3 + 20u)) +
+                        (odd ? tail : swap16(tail));
+                }
+                acc[j] = s;
+            }
+        }
+
+        // 3. block counts -> inclusive prefix over the wave
+        uint32_t P = nch;
+#pragma unroll
+        for (uint32_t o = 1; o < WAVE; o <<= 1) {
+            const uint32_t y = (uint32_t)__shfl_up((int)P, o);
+            if (lane >= o) P += y;
+        }
+        wd.dst[j] = (uint64_t)(uintptr_t)D;
+        wd.pfx[j] = P;
+        wd.len[j] = L;
+        wd.dmis[j] = dmis;
+        wd.cur[j] = cur;
+        wd.s1[j] = s1;
+        const uint32_t wtotal = (uint32_t)__shfl((int)P, (int)WAVE - 1);
+        if (lane == 0) wd.sub[wg] = wtotal;
+    }  // wg < PW
+    __syncthreads();
+    // subgroups 1.. continue the prefix of the ones before them
+    if (wg > 0 && wg < PW) {
+        uint32_t before = 0;
+        for (uint32_t t = 0; t < wg; ++t) before += wd.sub[t];
+        wd.pfx[wg * WAVE + lane] += before;
+    }
+    __syncthreads();
+    uint32_t total = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < PW; ++t) total += wd.sub[t];
+
+    // 4. the wave's blocks, 64 per step and UNROLL steps at a time: block k
+    //    belongs to the first packet whose inclusive prefix exceeds k
+    constexpr uint32_t U = UNROLL;
+    for (uint32_t k0 = wg * WAVE * U; k0 < total; k0 += W * WAVE * U) {
+        uint32_t q[U], c[U];
+        uint32_t fl[U];  // shift | extra << 4 | last << 5
+        u32x4 own[U], nb[U];
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+            const uint32_t k = k0 + u * WAVE + lane;
+            const bool valid = k < total;
+            uint32_t qq = 0;
+#pragma unroll
+            for (uint32_t step = NPOW / 2; step; step >>= 1)
+                if (wd.pfx[qq + step - 1] <= k) qq += step;
+            qq = valid ? qq : 0u;
+            const uint32_t end = wd.pfx[qq];
+            c[u] = valid ? k - (qq ? wd.pfx[qq - 1] : 0u) : 0xffffu;
+            q[u] = qq;
+            const bool last = SUMS && valid && (lane == WAVE - 1 || k + 1 >= end);
+            own[u] = u32x4{0u, 0u, 0u, 0u};
+            nb[u] = u32x4{0u, 0u, 0u, 0u};
+            uint64_t B = 0;       // the aligned block this lane loaded as `own` (0: none)
+            uint32_t sh = 0;
+            bool second = false;  // the funnel also needs block B + 16
+            if (valid) {
+                const uint32_t t = wd.len[qq];
+                const int32_t r0 = (int32_t)(16u * c[u]) - (int32_t)wd.dmis[qq];
+                const int32_t x0 = r0 - (int32_t)H;  // payload offset of the block's byte 0
+                const int32_t p0 = max(-x0, 0), p1 = min((int32_t)t - x0, 16);
+                if (p0 < p1) {
+                    const uint32_t xa = (uint32_t)(x0 + p0), xb = (uint32_t)(x0 + p1);
+                    uint32_t cs = wd.cur[qq], cx = wd.start[PIECES][qq];
+                    Piece p = piece_at(wd, ar, qq, xa, t, cs, cx);
+                    if (p.ok && p.end >= xb) {
+                        // one piece: k_emit's load path
+                        const uint64_t X = p.sbase + (uint64_t)(int64_t)x0;
+                        const uint64_t S0 = p.sbase + p.start, S1 = p.sbase + p.end;
+                        const uint64_t A = X & ~(uint64_t)15;
+                        sh = (uint32_t)X & 15u;
+                        if (A + 16 > S0 && A < S1) {
+                            own[u] = *(const __attribute__((address_space(1))) u32x4*)A;
+                            B = A;
+                        }
+                        second = sh != 0 && A + 16 < S1 && A + 32 > S0;
+                        if (second && B == 0) {  // only the second block holds bytes
+                            nb[u] = *(const __attribute__((address_space(1))) u32x4*)(A + 16);
+                            second = false;
+                            sh |= 16u;
+                        }
+                    } else {
+                        // a chunk boundary inside the block: piece by piece
+                        u32x4 o = u32x4{0u, 0u, 0u, 0u};
+                        uint32_t x = xa;
+                        while (p.ok) {
+                            const uint32_t e = min(p.end, xb);
+                            const u32x4 pv = piece_block(p, p.sbase + (uint64_t)(int64_t)x0);
+                            const int32_t b0 = (int32_t)x - x0, b1 = (int32_t)e - x0;
+                            o.x |= pv.x & below(b1) & ~below(b0);
+                            o.y |= pv.y & below(b1 - 4) & ~below(b0 - 4);
+                            o.z |= pv.z & below(b1 - 8) & ~below(b0 - 8);
+                            o.w |= pv.w & below(b1 - 12) & ~below(b0 - 12);
+                            x = e;
+                            if (x >= xb) break;
+                            p = piece_at(wd, ar, qq, x, t, cs, cx);
+                        }
+                        own[u] = o;
+                    }
+                }
+            }
+            // the next lane holds block B + 16 only if it loaded exactly that
+            const uint32_t nlo = from_next_lane((uint32_t)B), nhi = from_next_lane((uint32_t)(B >> 32));
+            const uint64_t NB = ((uint64_t)nhi << 32) | nlo;
+            if (second && NB != B + 16) {
+                nb[u] = *(const __attribute__((address_space(1))) u32x4*)(B + 16);
+                sh |= 16u;
+            }
+            fl[u] = sh | (last ? 32u : 0u);
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < U; ++u) {
+            const bool valid = c[u] != 0xffffu;
+            const uint32_t qq = q[u];
+            const uint32_t qd = wd.dmis[qq];
+            uint8_t* QD = (uint8_t*)(uintptr_t)wd.dst[qq];
+            const uint32_t QT = H + wd.len[qq];
+            const int32_t r0 = (int32_t)(16u * c[u]) - (int32_t)qd;
+            u32x4 n2;
+            n2.x = from_next_lane(own[u].x);
+            n2.y = from_next_lane(own[u].y);
+            n2.z = from_next_lane(own[u].z);
+            n2.w = from_next_lane(own[u].w);
+            u32x4 out = funnel(own[u], (fl[u] & 16u) ? nb[u] : n2, fl[u] & 15u);
+            if (H && valid && r0 < (int32_t)H) {
+                const u32x4 hb = *reinterpret_cast<const u32x4*>(regions + qq * RS + 16u * c[u]);
+                const int32_t hc = (int32_t)H - r0;
+                const uint32_t m0 = head_mask(hc, 0), m1 = head_mask(hc, 1),
+                               m2 = head_mask(hc, 2), m3 = head_mask(hc, 3);
+                out.x = (hb.x & m0) | (out.x & ~m0);
+                out.y = (hb.y & m1) | (out.y & ~m1);
+                out.z = (hb.z & m2) | (out.z & ~m2);
+                out.w = (hb.w & m3) | (out.w & ~m3);
+            }
+            bool parked = false;
+            if constexpr (SUMS) {
+                if (udp) {
+                    // as k_emit: the payload bytes of this block, a segmented
+                    // inclusive scan over the wave, the packet's share of this
+                    // step added in LDS by its last lane
+                    const int32_t p0 = max((int32_t)H - r0, 0), p1 = min((int32_t)QT - r0, 16);
+                    uint32_t s = (valid && p0 < p1) ? chunk_words(out, p0, p1) : 0u;
+#pragma unroll
+                    for (uint32_t o = 1; o < WAVE; o <<= 1) {
+                        const uint32_t y = (uint32_t)__shfl_up((int)s, o);
+                        if (lane >= o && o <= c[u]) s += y;
+                    }
+                    if ((fl[u] & 32u) && s) atomicAdd(&acc[qq], s);
+                    // the block(s) holding the field wait in LDS for the sum
+                    const uint32_t cf = (qd + fpos) >> 4;
+                    parked = valid && (c[u] == cf || c[u] == ((qd + fpos + 1u) >> 4));
+                    if (parked) park[(c[u] - cf) * NP + qq] = out;
+                }
+            }
+            if (valid && !parked) {
+                const int32_t t0 = r0 < 0 ? -r0 : 0;
+                const int32_t t1 = (int32_t)QT - r0 < 16 ? (int32_t)QT - r0 : 16;
+                if (t0 == 0 && t1 == 16) {
+                    *(__attribute__((address_space(1))) u32x4*)(QD + r0) = out;
+                } else {
+                    store_edge(QD + r0, out, t0, t1);
+                }
+            }
+        }
+    }
+    if constexpr (SUMS) {
+        if (!udp) return;
+        // 5. every block is summed once the group is here.  One lane per parked
+        //    block: fold the packet's sum, put the field's byte(s) that lie in
+        //    this block, and issue the block's only store.
+        __syncthreads();
+        if (threadIdx.x >= 2u * NP) return;
+        const uint32_t slot = threadIdx.x / NP, j = threadIdx.x % NP;
+        if (base + j >= a.n) return;
+        const uint32_t qd = wd.dmis[j];
+        const uint32_t cf = (qd + fpos) >> 4;
+        if (slot && ((qd + fpos + 1u) >> 4) == cf) return;  // the field sits in one block
+        const uint32_t c = cf + slot;
+        u32x4 out = park[slot * NP + j];
+        const uint32_t QT = H + wd.len[j];
+        if (QT - a.sums.udp_at <= 65535u) {
+            const uint32_t f = fold16(acc[j]);
+            uint32_t sum = ~((qd & 1u) ? f : swap16(f)) & 0xffffu;
+            sum = sum ? sum : 0xffffu;
+            const int32_t pos = (int32_t)(qd + fpos) - (int32_t)(16u * c);
+            put_byte(out, pos, sum >> 8);
+            put_byte(out, pos + 1, sum & 0xffu);
+        }
+        uint8_t* QD = (uint8_t*)(uintptr_t)wd.dst[j];
+        const int32_t r0 = (int32_t)(16u * c) - (int32_t)qd;
+        const int32_t t0 = r0 < 0 ? -r0 : 0;
+        const int32_t t1 = (int32_t)QT - r0 < 16 ? (int32_t)QT - r0 : 16;
+        if (t0 == 0 && t1 == 16) {
+            *(__attribute__((address_space(1))) u32x4*)(QD + r0) = out;
+        } else {
+            store_edge(QD + r0, out, t0, t1);
+        }
+    }
+}
+
+// Dynamic LDS of one k_emit_read block for a header block of H bytes.
+template <bool SUMS>
+constexpr size_t emit_read_smem(uint32_t H) {
+    return (INGOT_MAX_EMIT_HDR / 16 + 4) * 16 + sizeof(ReadDesc) + NP * region_bytes(H) +
+           (SUMS ? NP * SUM_LDS_PER_PACKET : 0u);
+}
+// gfx950: 160 KiB of LDS per workgroup.
+static_assert(emit_read_smem<true>(INGOT_MAX_EMIT_HDR) <= 160u * 1024u, "k_emit_read LDS > 160 KiB");
+static_assert(BLOCK >= 2 * NP, "sums: one lane per parked block");
+
+template <bool SUMS>
+hipError_t go(const EmitReadArgs& a, hipStream_t s) {
+    const uint64_t blocks = (a.e.n + NP - 1) / NP;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((k_emit_read<SUMS>), dim3((uint32_t)blocks), dim3(BLOCK),
+                       emit_read_smem<SUMS>(a.e.hdr_len), s, a);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+size_t emit_read_lds_bytes(const EmitReadArgs& a) {
+    return (a.e.sums.v4 || a.e.sums.udp) ? emit_read_smem<true>(a.e.hdr_len)
+                                         : emit_read_smem<false>(a.e.hdr_len);
+}
+
+hipError_t launch_emit_read(const EmitReadArgs& a, hipStream_t s) {
+    if (a.e.n == 0) return hipSuccess;
+    return (a.e.sums.v4 || a.e.sums.udp) ? go<true>(a, s) : go<false>(a, s);
+}
+
+}  // namespace ingot_gpu

@@ -1,7 +1,7 @@
 // kernels.h — internal interface between the C ABI (api.cpp) and the HIP
 // kernels: the argument blocks, the tuning record and the launchers of
 // parse.hip, read.hip, ring.hip, tuple.hip, packed.hip, flow.hip, header.hip,
-// emit.hip, csum.hip and stream.hip.  Not part of the public ABI.
+// emit.hip, emit_read.hip, csum.hip and stream.hip.  Not part of the public ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -179,6 +179,22 @@ static_assert(sizeof(EmitArgs) <= 4096, "EmitArgs exceeds the 4 KiB kernel-argum
 // bytes of dynamic LDS one emit block needs (checked against the device)
 size_t emit_lds_bytes(const EmitArgs& a);
 hipError_t launch_emit(const EmitArgs& a, hipStream_t s);
+
+// Emit over parse_read's chunk tables (ingot_gpu_emit_packets_read,
+// k_emit_read in emit_read.hip).  `e` is what emit_args / emit_sums made of the
+// header block; e.src is the chunk arena, e.off / e.len / e.stride are unused.
+struct EmitReadArgs {
+    EmitArgs e;
+    const uint64_t* seg_off;   // per chunk
+    const uint16_t* seg_len;   // per chunk
+    const uint32_t* pkt_seg;   // n+1 chunk-index bounds
+    const uint16_t* from;      // optional: first logical byte taken
+    const uint16_t* take;      // optional: at most this many bytes
+    uint16_t* taken;           // optional: payload bytes written
+};
+static_assert(sizeof(EmitReadArgs) <= 4096, "EmitReadArgs exceeds the 4 KiB kernel-argument limit");
+size_t emit_read_lds_bytes(const EmitReadArgs& a);
+hipError_t launch_emit_read(const EmitReadArgs& a, hipStream_t s);
 
 // Batched Internet checksums (ingot_gpu_checksum_verify / _fill, csum.hip).
 struct CsumArgs {

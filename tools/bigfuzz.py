@@ -16,10 +16,13 @@ Python model of tests/emit_csum_model.py, same cap), and the checksum calls
 over chunked packets (`csum_read`, only with --only: verify, fill, verify again
 over cut generator frames against tests/csum_read_model.py, same cap), and the
 rewrite over chunked packets (`modify_read`, only with --only: random edit
-lists over cut generator frames against tests/modify_read_model.py, same cap).
+lists over cut generator frames against tests/modify_read_model.py, same cap),
+and the emit over chunked packets (`emit_read`, only with --only: every header
+stack in front of cut generator frames with random from / take, whole arenas
+against tests/emit_read_model.py, same cap).
 
     python tools/bigfuzz.py [--frames 4000000] [--seed 1234]
-                            [--only csum|modify_csum|emit_csum|csum_read|modify_read]
+                            [--only csum|modify_csum|emit_csum|csum_read|modify_read|emit_read]
 """
 from __future__ import annotations
 
@@ -336,6 +339,70 @@ def modify_read_cases(ctx, n, seed, res):
         torch.cuda.empty_cache()
 
 
+def emit_read_cases(ctx, n, seed, res):
+    """ingot_gpu_emit_packets_read against tests/emit_read_model.py: every
+    header stack of tests/emit_csum_cases.py in front of the frames of four
+    generator profiles cut by tests/csum_read_cases.py's `cut` (up to 9
+    chunks, empty ones included, every chunk at its own misalignment), with
+    random d_from / d_take (half of the packets whole); the whole destination
+    arena and d_taken are compared."""
+    import torch
+
+    import ingot_amd
+    from ingot_amd import Chain, GenProfile
+    from tests import csum_read_cases as chunks
+    from tests import emit_csum_cases as cases
+    from tests import emit_read_model as model
+
+    def dev(a):
+        a = np.ascontiguousarray(a)
+        signed = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32,
+                  np.dtype(np.uint64): np.int64}
+        return torch.from_numpy(a.view(signed.get(a.dtype, a.dtype))).cuda()
+
+    rng = np.random.default_rng(seed)
+    pairs = ((GenProfile.MIXED, Chain.GenericUlp), (GenProfile.VLAN_V6EH, Chain.VlanUlp),
+             (GenProfile.ADVERSARIAL, Chain.GenericUlp),
+             (GenProfile.GENEVE, Chain.GeneveOverV6Tunnel))
+    for k, (prof, chain) in enumerate(pairs):
+        arena, off, lens = ingot_amd.gen_frames(prof, n, seed=seed + 150 + k)
+        crec = ingot_amd.records_to_numpy(ctx.parse(arena, off, lens, chain))
+        ln = lens.cpu().numpy()
+        frames = chunks.frames_of(arena.cpu().numpy(), off.cpu().numpy().view(np.uint64), ln)
+        packets = [chunks.cut(f, crec[i], rng) for i, f in enumerate(frames)]
+        tables = chunks.place(packets, misalign=list(range(16)) + [int(rng.integers(16))],
+                              gap=int(rng.integers(0, 4)))
+        d_tab = [dev(x) for x in tables]
+        del arena, off, lens
+        for name in cases.STACKS:
+            hdr, sets, sums = cases.stack(name, n, rng)
+            whole = rng.random(n) < 0.5
+            frm = np.where(whole, 0, rng.integers(0, ln.astype(np.int64) + 10)).astype(np.uint16)
+            take = np.where(rng.random(n) < 0.5, 65535,
+                            rng.integers(0, ln.astype(np.int64) + 10)).astype(np.uint16)
+            t = model.linearise(*tables, frm, take)[2]
+            dst_off, size = cases.pack(t, len(hdr), rng)
+            want, lens_want = model.apply(np.full(size, 0xA5, np.uint8), hdr, sets, sums, *tables,
+                                          dst_off, frm, take)
+            dst = dev(np.full(size, 0xA5, np.uint8))
+            taken = dev(np.full(n, 0xA5A5, np.uint16))
+            dsets = [s if len(s) == 4 else (*s[:4], dev(s[4])) for s in sets]
+            ctx.emit_packets_read(hdr, dsets, *d_tab, dst, dev(dst_off), frm=dev(frm),
+                                  take=dev(take), taken=taken, sums=sums)
+            torch.cuda.synchronize()
+            key = f"emit_read/{prof.name}/{name}"
+            res[key] = {"byte_mismatches": int((dst.cpu().numpy() != want).sum()),
+                        "taken_mismatches": int((taken.cpu().numpy().view(np.uint16)
+                                                 != lens_want).sum()),
+                        "arena_bytes": size, "chunks": int(tables[3][-1]),
+                        "chunks_per_packet_max": int(np.diff(tables[3].astype(np.int64)).max()),
+                        "packets_cut_short": int((t < ln).sum())}
+            print(key, res[key], flush=True)
+            del dst, taken
+        del d_tab
+        torch.cuda.empty_cache()
+
+
 def finish(n, seed, t0, res):
     out = {"frames_per_case": n, "seed": seed, "wall_s": round(time.time() - t0, 1),
            "cases": res,
@@ -352,16 +419,16 @@ def main():
     ap.add_argument("--csum-frames", type=int, default=200_000,
                     help="frames per csum case (its reference is a Python model)")
     ap.add_argument("--only", default="",
-                    help="'csum' / 'modify_csum' / 'emit_csum' / 'csum_read' / 'modify_read': "
-                         "run only that case group")
+                    help="'csum' / 'modify_csum' / 'emit_csum' / 'csum_read' / 'modify_read' / "
+                         "'emit_read': run only that case group")
     args = ap.parse_args()
-    if args.only in ("csum", "modify_csum", "emit_csum", "csum_read", "modify_read"):
+    if args.only in ("csum", "modify_csum", "emit_csum", "csum_read", "modify_read", "emit_read"):
         import ingot_amd
 
         res, t0 = {}, time.time()
         group = {"csum": csum_cases, "modify_csum": modify_csum_cases,
                  "emit_csum": emit_csum_cases, "csum_read": csum_read_cases,
-                 "modify_read": modify_read_cases}[args.only]
+                 "modify_read": modify_read_cases, "emit_read": emit_read_cases}[args.only]
         group(ingot_amd.Context(0), min(args.frames, args.csum_frames), args.seed, res)
         return finish(min(args.frames, args.csum_frames), args.seed, t0, res)
 

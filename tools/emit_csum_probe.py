@@ -19,11 +19,30 @@ library and of another build (`--against NAME`: tools/variants/NAME, e.g. the
 parent commit from tools/build_tree_variant.sh), so that a change of the
 plain kernel would show.
 
+`--read` measures ingot_gpu_emit_packets_read instead: the
+same frames cut in place at payload_off into two chunks (the whole frame and
+an empty chunk where the record is not Ok), rows
+
+  a  emit               as above;
+  b  emit_csum          as above;
+  c  two_launch         what the chunked caller had before: emit_packets(hdr,
+                        chunk 0), then emit_packets(no header, chunk 1) behind
+                        it (the two length fields as per-packet U16 values,
+                        since LENGTH would count chunk 0 alone);
+  d  read               ingot_gpu_emit_packets_read, the same tables, no sums;
+  e  two_launch_fill    c + the UDP_PARSER parse + ingot_gpu_checksum_fill(L4);
+  f  read_csum          ingot_gpu_emit_packets_read with the outer UDP sum;
+  d1 / f1               d and f with every packet one chunk (what the tables
+                        cost against a and b);
+
+checks once that c and d, and e and f, leave identical bytes, and compares the
+rounds' ranges: the new row's maximum against the old row's minimum.
+
 `--usage-only` compiles ingot_amd/csrc/emit.hip with
 -Rpass-analysis=kernel-resource-usage and writes the kernels' figures (no GPU
 needed); `--usage FILE` attaches such a file to the result.
 
-    python tools/emit_csum_probe.py [--frames N] [--reps 5] [--rounds 5]
+    python tools/emit_csum_probe.py [--frames N] [--reps 5] [--rounds 5] [--read]
         [--against head] [--usage FILE] [--out profiles/r12_emit_csum_probe.json]
 """
 from __future__ import annotations
@@ -41,14 +60,18 @@ sys.path.insert(0, str(ROOT))
 
 
 def resource_usage() -> dict:
-    """k_emit's instantiations -> registers, scratch, occupancy (from hipcc)."""
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-           f"-I{ROOT / 'include'}", "-Rpass-analysis=kernel-resource-usage", "-c",
-           str(ROOT / "ingot_amd" / "csrc" / "emit.hip"), "-o", "/dev/null"]
-    err = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
+    """k_emit's and k_emit_read's instantiations -> registers, scratch,
+    occupancy (from hipcc)."""
+    err = ""
+    for src in ("emit.hip", "emit_read.hip"):
+        cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
+               f"-I{ROOT / 'include'}", "-Rpass-analysis=kernel-resource-usage", "-c",
+               str(ROOT / "ingot_amd" / "csrc" / src), "-o", "/dev/null"]
+        err += subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
     out, cur = {}, None
-    names = {"ILb1ELb1EE": "k_emit<copy, sums>", "ILb1ELb0EE": "k_emit<copy>",
-             "ILb0ELb0EE": "k_emit<headers>"}
+    names = {"k_emitILb1ELb1EE": "k_emit<copy, sums>", "k_emitILb1ELb0EE": "k_emit<copy>",
+             "k_emitILb0ELb0EE": "k_emit<headers>", "k_emit_readILb1EE": "k_emit_read<sums>",
+             "k_emit_readILb0EE": "k_emit_read"}
     for line in err.splitlines():
         m = re.search(r"remark: +([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+)", line)
         if not m:
@@ -57,7 +80,8 @@ def resource_usage() -> dict:
         if key == "Function Name":
             cur = next((v for k, v in names.items() if k in val), val)
             out[cur] = {}
-        elif cur and key in ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "Occupancy"):
+        elif cur and key in ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "Occupancy",
+                             "SGPRs Spill", "VGPRs Spill"):
             out[cur][key] = int(val)
     return out
 
@@ -190,6 +214,91 @@ def child_main(args) -> dict:
             "b_beats_c_by_more_than_spread": bool(b < c * (1 - spread))}
 
 
+def child_read(args) -> dict:
+    import torch
+
+    from ingot_amd import CSUM_L4, Chain, EmitSource, Field
+
+    d = setup(args.frames, args.copies)
+    ctx, n, H = d["ctx"], args.frames, d["H"]
+    arena, off, lens, hdr, dst_off = d["arena"], d["off"], d["lens"], d["hdr"], d["dst_off"]
+    recs = torch.empty((n, 16), dtype=torch.uint8, device="cuda")
+    # the frames cut in place at payload_off (tools/csum_probe.py --read's tables)
+    rc = ctx.parse(arena, off, lens, Chain.GenericUlp)
+    L = lens.to(torch.int32) & 0xFFFF
+    pay = rc[:, 12].to(torch.int32) | (rc[:, 13].to(torch.int32) << 8)
+    pay = torch.where(rc[:, 0] == 0, torch.minimum(pay, L), L)
+    o0, o1 = off.contiguous(), (off + pay.to(torch.int64)).contiguous()
+    l0, l1 = pay.to(torch.int16).contiguous(), (L - pay).to(torch.int16).contiguous()
+    so = torch.stack((o0, o1), dim=1).reshape(-1).contiguous()
+    sl = torch.stack((l0, l1), dim=1).reshape(-1).contiguous()
+    ps1 = torch.arange(n + 1, dtype=torch.int32, device="cuda")
+    ps2 = (ps1 * 2).contiguous()
+    dst_off1 = (dst_off + H + pay.to(torch.int64)).contiguous()
+    # the two-launch path cannot use LENGTH (it would count chunk 0 alone)
+    sets_c = [(14, Field.V6_PAYLOAD_LEN, EmitSource.U16, 0, (L + (H - 54)).to(torch.int16)),
+              (54, Field.UDP_LENGTH, EmitSource.U16, 0, (L + (H - 54)).to(torch.int16)),
+              d["sets"][2], d["sets"][3]]
+
+    def pick(dst):
+        return d["pick"]() if dst is None else dst
+
+    def emit(dst=None):
+        ctx.emit_packets(hdr, d["sets"], arena, off, lens, pick(dst), dst_off)
+
+    def emit_csum(dst=None):
+        ctx.emit_packets(hdr, d["sets"], arena, off, lens, pick(dst), dst_off, sums=d["sums"])
+
+    def two_launch(dst=None):
+        dst = pick(dst)
+        ctx.emit_packets(hdr, sets_c, arena, o0, l0, dst, dst_off)
+        ctx.emit_packets(b"", [], arena, o1, l1, dst, dst_off1)
+        return dst
+
+    def two_launch_fill(dst=None):
+        dst = two_launch(dst)
+        ctx.parse(dst, dst_off, d["tl"], Chain.UdpParser, out=recs)
+        ctx.checksum_fill(dst, dst_off, d["tl"], recs, CSUM_L4)
+
+    def read(dst=None):
+        ctx.emit_packets_read(hdr, d["sets"], arena, so, sl, ps2, pick(dst), dst_off)
+
+    def read_csum(dst=None):
+        ctx.emit_packets_read(hdr, d["sets"], arena, so, sl, ps2, pick(dst), dst_off,
+                              sums=d["sums"])
+
+    def read_1chunk(dst=None):
+        ctx.emit_packets_read(hdr, d["sets"], arena, off, lens, ps1, pick(dst), dst_off)
+
+    def read_csum_1chunk(dst=None):
+        ctx.emit_packets_read(hdr, d["sets"], arena, off, lens, ps1, pick(dst), dst_off,
+                              sums=d["sums"])
+
+    x, y = d["dsts"][0], d["dsts"][1 % len(d["dsts"])]
+    same = {}
+    for name, old, new in (("c_equals_d", two_launch, read), ("e_equals_f", two_launch_fill, read_csum),
+                           ("a_equals_d1", emit, read_1chunk), ("b_equals_f1", emit_csum, read_csum_1chunk)):
+        x.fill_(0xA5)
+        y.fill_(0xA5)
+        old(x)
+        new(y)
+        torch.cuda.synchronize()
+        same[name] = bool(torch.equal(x, y)) if x is not y else None
+    runs = timed({"a_emit": emit, "b_emit_csum": emit_csum, "c_two_launch": two_launch,
+                  "d_read": read, "e_two_launch_fill": two_launch_fill, "f_read_csum": read_csum,
+                  "d1_read_1chunk": read_1chunk, "f1_read_csum_1chunk": read_csum_1chunk},
+                 args.reps, args.rounds)
+    for r in runs.values():
+        r["min"], r["max"] = min(r["rounds"]), max(r["rounds"])
+    return {"frames": n, "hdr_len": H, "payload_bytes": d["payload"], "emitted_bytes": d["total"],
+            "chunks": {"two": 2 * n, "one": n}, "empty_second_chunks": int((l1 == 0).sum().item()),
+            "copies": args.copies, "reps": args.reps, "same_bytes": same, "runs": runs,
+            "d_max_le_c_min": bool(runs["d_read"]["max"] <= runs["c_two_launch"]["min"]),
+            "f_max_le_e_min": bool(runs["f_read_csum"]["max"] <= runs["e_two_launch_fill"]["min"]),
+            "d1_over_a": round(runs["d1_read_1chunk"]["us"] / runs["a_emit"]["us"], 4),
+            "f1_over_b": round(runs["f1_read_csum_1chunk"]["us"] / runs["b_emit_csum"]["us"], 4)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=1 << 23)
@@ -202,11 +311,13 @@ def main():
     ap.add_argument("--usage-only", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None)
+    ap.add_argument("--read", action="store_true", help="the chunked emit's rows (DESIGN 4.12)")
     args = ap.parse_args()
     if args.usage_only:
         out = resource_usage()
     elif args.child:
         print(json.dumps(child_main(args) if args.child == "main"
+                         else child_read(args) if args.child == "read"
                          else child_plain(args.child, args)), flush=True)
         return
     else:
@@ -220,7 +331,7 @@ def main():
                 sys.exit(p.returncode or 1)
             return json.loads(p.stdout.strip().splitlines()[-1])
 
-        out = {"what": __doc__.split("\n\n")[0], **run("main")}
+        out = {"what": __doc__.split("\n\n")[0], **run("read" if args.read else "main")}
         print(json.dumps(out), flush=True)
         if args.against:
             rows = []
