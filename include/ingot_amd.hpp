@@ -595,6 +595,40 @@ inline std::vector<Modified> modify_batch(Context& ctx,
     return out;
 }
 
+// The rewrite with per-packet operands (ingot_gpu_parse_modify_rows): the
+// frames, the tables and d_row already live on the device (a NAT table is the
+// host's own structure, uploaded once), so this wrapper only builds the edit
+// list and turns an error code into an exception.  edit_rows: `d_values` is
+// the table (plus a member's offset), `pitch` its row size (0: a dense array
+// of the source's width); INGOT_EDIT_VALUE takes `value` and no table.
+inline ingot_edit_rows edit_rows(uint8_t layer, int field, int op, int source, int by,
+                                 const void* d_values, uint32_t pitch = 0, uint32_t value = 0,
+                                 uint8_t index = 0) {
+    ingot_edit_rows e{};
+    e.layer = layer;
+    e.field = (uint8_t)field;
+    e.op = (uint8_t)op;
+    e.index = index;
+    e.value = value;
+    e.source = (uint8_t)source;
+    e.by = (uint8_t)by;
+    e.pitch = pitch;
+    e.d_values = d_values;
+    return e;
+}
+
+inline void parse_modify_rows(Context& ctx, uint8_t* d_arena, const uint64_t* d_off,
+                              const uint16_t* d_len, uint32_t stride, uint64_t n, int chain,
+                              const std::vector<ingot_edit_rows>& edits,
+                              const uint32_t* d_row = nullptr, uint32_t n_rows = 0,
+                              uint32_t what = 0, ingot_rec* d_out = nullptr,
+                              hipStream_t stream = nullptr) {
+    check(ingot_gpu_parse_modify_rows(ctx.get(), d_arena, d_off, d_len, stride, n, chain,
+                                      edits.data(), (uint32_t)edits.size(), d_row, n_rows, what,
+                                      d_out, stream),
+          "ingot_gpu_parse_modify_rows");
+}
+
 // The same setters over chunk lists (ingot_gpu_parse_read_modify, what != 0:
 // ingot_gpu_parse_read_modify_csum): packet i = packets[i], parsed with
 // parse_read's chunk semantics and, when Ok, edited in place at the record's

@@ -40,8 +40,8 @@ extern "C" {
 
 /* 4: ingot_gpu_checksum_verify / ingot_gpu_checksum_fill (ingot_csum);
  *    ingot_gpu_parse_modify_csum, ingot_gpu_checksum_verify_read / _fill_read,
- *    ingot_gpu_parse_read_modify / ingot_gpu_parse_read_modify_csum
- *    (added calls: the number stays).
+ *    ingot_gpu_parse_read_modify / ingot_gpu_parse_read_modify_csum,
+ *    ingot_gpu_parse_modify_rows (added calls: the number stays).
  * 3: ingot_gpu_comm_wrap (borrow the host's RCCL communicator).
  * 2: ingot_gpu_comm_* / ingot_gpu_flow_hist_allreduce (config 5's reduce);
  *    host mappings counted per map, ingot_gpu_host_unmap EINVAL for a pointer
@@ -1198,6 +1198,122 @@ int ingot_gpu_parse_modify_csum(ingot_gpu_ctx* ctx, uint8_t* d_arena,
                                 const uint64_t* d_off, const uint16_t* d_len,
                                 uint32_t stride, uint64_t n, int chain,
                                 const ingot_edit* edits, uint32_t n_edits,
+                                uint32_t what, ingot_rec* d_out, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The rewrite with per-packet operands: ingot_gpu_parse_modify (and, with
+ * `what`, ingot_gpu_parse_modify_csum) whose edits take their operand from
+ * device tables instead of one constant per batch, and which can set the
+ * Ethernet and IPv6 addresses (ingot's `set_destination` / `set_source` on
+ * Ethernet and Ipv6, ethernet.rs / ip.rs).  A NAT that maps each flow to its
+ * own address and port, a next-hop MAC per packet, NAT66, a per-connection
+ * TCP sequence offset.  Build-defined; tests/modify_rows_model.py is the
+ * definition.
+ *
+ * Frames, parse, records.  The frames (d_off NULL selects the strided layout),
+ * the parse, the records, the layer / kind matching and the order of the edits
+ * are ingot_gpu_parse_modify's: only packets that parse Ok are edited, and a
+ * later edit sees what earlier ones wrote.  `edits` is host memory
+ * (<= INGOT_MAX_EDITS).
+ *
+ * Fields.  `field` is an ingot_field, or one of the wide fields of
+ * ingot_wide_field, which exist only here: the Ethernet destination / source
+ * (6 B at header + 0 / + 6; layer 0, and the tunnel chain's inner Ethernet at
+ * layer 4) and the IPv6 source / destination (16 B at header + 8 / + 24; the
+ * L3 layer when it is IPv6, and the tunnel chain's outer IPv6 at layer 1).
+ *
+ * Operand of edit k for packet i, by `source`:
+ *   INGOT_EDIT_VALUE  `value`, for every packet (ingot_edit's meaning);
+ *   otherwise the row index is r = i (INGOT_BY_PACKET) or d_row[i]
+ *   (INGOT_BY_ROW) and the row is (const uint8_t*)d_values + r * pitch
+ *   (pitch 0: the source's width, i.e. a dense array);
+ *   INGOT_EDIT_U16 / _U32  the host-endian integer at the row, zero-extended,
+ *       used exactly as `value` would be, with any op, wrapping modulo
+ *       2^width;
+ *   INGOT_EDIT_BYTES  the field's bytes in wire order (6 or 16) at the row.
+ *       BYTES is valid only for wide fields, wide fields take only BYTES, and
+ *       wide fields take only INGOT_OP_SET.
+ * Several edits may point into one table at different offsets (d_values = the
+ * table + the member's offset, pitch = the row size).
+ *
+ * Row guard.  With d_row given, a packet whose d_row[i] >= n_rows is not
+ * touched at all: no edit is applied (not even a VALUE one), no checksum is
+ * updated and no table is read for it; its record is still written.
+ * INGOT_ROW_NONE is the largest such value, so the d_flow array of
+ * ingot_gpu_flow_hist (INGOT_FLOW_NONE for packets that are not counted) can
+ * be passed as d_row with a table of `bins` rows.  With d_row NULL no edit may
+ * be BY_ROW (EINVAL) and n_rows is ignored.  Table reads are bounded by the
+ * row guard alone: a BY_PACKET table holds n rows, a BY_ROW table n_rows.
+ *
+ * Bytes written: exactly what ingot_gpu_parse_modify writes for the same
+ * fields (whole write-back sectors of the staged copy, as there), plus the two
+ * bytes of each updated sum.  The tables and d_row are only read; they may be
+ * shared between concurrent calls.
+ *
+ * Checksums.  what == 0: none.  Otherwise `what`, the three sums, RFC 1624
+ * eqn. 3, the UDP rules, the later-fragment rule and the refused fields are
+ * ingot_gpu_parse_modify_csum's, with these covered ranges in addition:
+ *   - the IPv6 source and destination (l3_off + 8 .. + 40) feed the L4 sum
+ *     where ingot_gpu_checksum_fill sums an IPv6 pseudo-header (TCP, UDP,
+ *     ICMPv6; not ICMPv4);
+ *   - in the tunnel chain, the outer IPv6 addresses (layer 1) feed OUTER_L4 as
+ *     its pseudo-header, and the inner Ethernet addresses (layer 4) and the
+ *     inner IPv6 addresses (layer 5) feed OUTER_L4 as covered bytes;
+ *   - Ethernet addresses at layer 0 feed nothing.
+ *
+ * EINVAL, all checked before any device work, in this order:
+ *   1. ingot_gpu_parse_modify's own checks (ctx, chain, n_edits >
+ *      INGOT_MAX_EDITS, a NULL list);
+ *   2. per edit: an unknown field or op, or a layer out of range; a bad
+ *      `source` or `by`; non-zero `_pad`; non-zero `value` with a table
+ *      source; NULL d_values with a table source; BYTES on a narrow field, or
+ *      another source on a wide field; a wide field with an op other than SET;
+ *      `pitch` non-zero and below the source's width; U16 / U32 with d_values
+ *      or pitch not a multiple of 2 / 4; BY_ROW without d_row;
+ *   3. `what`: bits above 7, or OUTER_L4 outside the tunnel chain; with
+ *      what != 0, the refused fields;
+ *   4. n == 0 succeeds;
+ *   5. a NULL arena, the slots' stride / alignment rules, d_off without d_len.
+ *
+ * Out of scope: the slot-ring kernel (slots >= 64 B without a length array
+ * run the plain per-tile kernel here, whatever INGOT_TUNE_PIPELINE says); the
+ * chunked form (ingot_gpu_parse_read_modify takes no tables); ops other than
+ * SET on wide fields; wide fields in ingot_edit and in the emit calls.
+ * ------------------------------------------------------------------------- */
+enum ingot_wide_field {            /* only valid in ingot_edit_rows.field */
+    INGOT_FW_ETH_DESTINATION = 64, /* ethernet.rs, 6 B at +0  */
+    INGOT_FW_ETH_SOURCE      = 65, /* 6 B at +6  */
+    INGOT_FW_V6_SOURCE       = 66, /* ip.rs Ipv6, 16 B at +8  */
+    INGOT_FW_V6_DESTINATION  = 67  /* 16 B at +24 */
+};
+enum ingot_edit_source {
+    INGOT_EDIT_VALUE = 0, INGOT_EDIT_U16 = 1, INGOT_EDIT_U32 = 2, INGOT_EDIT_BYTES = 3
+};
+enum ingot_edit_by { INGOT_BY_PACKET = 0, INGOT_BY_ROW = 1 };
+#define INGOT_ROW_NONE 0xffffffffu
+
+typedef struct ingot_edit_rows {
+    uint8_t layer;         /* as ingot_edit */
+    uint8_t field;         /* enum ingot_field or enum ingot_wide_field */
+    uint8_t op;            /* enum ingot_edit_op */
+    uint8_t index;         /* as ingot_edit */
+    uint32_t value;        /* VALUE: the operand; otherwise must be 0 */
+    uint8_t source;        /* enum ingot_edit_source */
+    uint8_t by;            /* enum ingot_edit_by */
+    uint16_t _pad;         /* must be 0 */
+    uint32_t pitch;        /* bytes between rows; 0 = the source's width */
+    const void* d_values;  /* device memory; NULL only for VALUE */
+} ingot_edit_rows;
+
+#ifdef __cplusplus
+static_assert(sizeof(ingot_edit_rows) == 24, "ingot_edit_rows is 24 bytes");
+#endif
+
+int ingot_gpu_parse_modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena,
+                                const uint64_t* d_off, const uint16_t* d_len,
+                                uint32_t stride, uint64_t n, int chain,
+                                const ingot_edit_rows* edits, uint32_t n_edits,
+                                const uint32_t* d_row, uint32_t n_rows,
                                 uint32_t what, ingot_rec* d_out, void* stream);
 
 /* ---------------------------------------------------------------------------

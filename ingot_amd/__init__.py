@@ -53,11 +53,17 @@ from .abi import (  # noqa: F401  (re-exports)
     IngotRec8,
     L3Kind,
     L4Kind,
+    EditBy,
     EditOp,
+    EditSource,
     EmitSource,
     EmitSum,
     Field,
     ParseError,
+    ROW_NONE,
+    WIDE_BYTES,
+    WideField,
+    edit_rows_array,
     edits_array,
     emit_sets_array,
     emit_sums_array,
@@ -502,6 +508,90 @@ class Context:
             self._h, _ptr(arena), _ptr(off), _ptr(lens), int(stride), n, int(chain),
             e.ctypes.data_as(ctypes.c_void_p), len(e), _ptr(out), _stream(stream, self.device)),
             "ingot_gpu_parse_modify")
+        return out
+
+    def _edit_rows(self, edits, n: int, rows, n_rows: int):
+        """parse_modify_rows' edit list -> (ingot_edit_rows array, tensors kept
+        alive for the call).  Every table is validated here, on the host:
+        dtype, unit stride in its last dimension, a row stride that holds the
+        source's width, and enough rows for the packets (by packet) or for
+        n_rows (by row)."""
+        out, keep = [], []
+        for k, e in enumerate(edits):
+            layer, field, op, operand = e[0], e[1], e[2], e[3]
+            index = e[4] if len(e) > 4 else 0
+            by = EditBy.PACKET
+            if isinstance(operand, tuple):
+                if len(operand) != 2 or operand[0] != "row":
+                    raise ValueError(f"edit {k}: a table operand is a tensor or ('row', tensor)")
+                if rows is None:
+                    raise ValueError(f"edit {k}: ('row', tensor) needs `rows`")
+                by, operand = EditBy.ROW, operand[1]
+            wide = int(field) in WIDE_BYTES
+            if not hasattr(operand, "data_ptr"):
+                if wide:
+                    raise ValueError(f"edit {k}: a wide field takes a 2-D uint8 tensor")
+                out.append((layer, field, op, index, int(operand) & 0xFFFFFFFF, EditSource.VALUE,
+                            EditBy.PACKET, 0, 0))
+                continue
+            t, name = operand, f"edit {k}'s table"
+            dt = str(t.dtype).replace("torch.", "")
+            if wide:
+                width = WIDE_BYTES[WideField(int(field))]
+                if dt != "uint8" or t.dim() != 2 or t.shape[1] != width:
+                    raise ValueError(f"{name} must be uint8 of shape (rows, {width}), not {dt} "
+                                     f"{tuple(t.shape)}")
+                source = EditSource.BYTES
+            else:
+                if dt not in _U16 + _U32:
+                    raise ValueError(f"{name} must be {' or '.join(_U16 + _U32)}, not {dt}")
+                if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] != 1):
+                    raise ValueError(f"{name} must have shape (rows,) or (rows, 1)")
+                source = EditSource.U16 if dt in _U16 else EditSource.U32
+                width = 2 if dt in _U16 else 4
+            if t.shape[-1] > 1 and t.stride(-1) != 1:
+                raise ValueError(f"{name} must be contiguous in its last dimension")
+            pitch = t.stride(0) * t.element_size() if t.shape[0] > 1 else width
+            if pitch < width:
+                raise ValueError(f"{name}: rows {pitch} B apart cannot hold {width} B")
+            need = n_rows if by == EditBy.ROW else n
+            if t.shape[0] < need:
+                raise ValueError(f"{name} holds {t.shape[0]} rows, needs at least {need}")
+            self._on_device(**{name: t})
+            keep.append(t)
+            out.append((layer, field, op, index, 0, source, by, pitch, t.data_ptr()))
+        return edit_rows_array(out), keep
+
+    def parse_modify_rows(self, arena, off, lens, chain: Chain, edits, rows=None,
+                          n_rows: int = 0, stride: int = 0, n: Optional[int] = None, out=None,
+                          csum: int = 0, stream=None):
+        """parse_modify with per-packet operands (ingot_gpu_parse_modify_rows):
+        edits = [(layer, Field | WideField, EditOp, operand[, vlan index]), ...].
+        `operand` is an int (the same value for every packet) or a cuda tensor
+        with one row per packet: uint16 / int16 (U16) or uint32 / int32 (U32)
+        of shape (rows,) or (rows, 1), or, for a WideField, uint8 of shape
+        (rows, 6 | 16) holding the bytes in wire order.  A tensor's row stride
+        is the table's pitch, so columns of one (rows, 32) uint8 NAT table can
+        be passed as views.  ("row", tensor) takes row rows[i] instead of row
+        i: `rows` holds n uint32 values, and a packet whose rows[i] >= n_rows
+        (ROW_NONE, flow_hist's bin of an uncounted packet) is left untouched.
+
+        csum != 0: the same launch updates those checksums (RFC 1624).
+        Returns `out` ((n, 16) uint8 records) if given, else None."""
+        if n is None:
+            n = off.numel()
+        self._frames(arena, off, lens, stride, n)
+        self._arg("out", out, _U8, n * REC_BYTES, optional=True)
+        self._arg("rows", rows, _U32, n, optional=True)
+        if rows is not None and (n_rows < 0 or n_rows > 0xFFFFFFFF):
+            raise ValueError("n_rows must fit 32 bits")
+        e, keep = self._edit_rows(edits, n, rows, int(n_rows))
+        self._on_device(arena=arena, off=off, lens=lens, out=out, rows=rows)
+        _lib.check(self._lib.ingot_gpu_parse_modify_rows(
+            self._h, _ptr(arena), _ptr(off), _ptr(lens), int(stride), n, int(chain),
+            e.ctypes.data_as(ctypes.c_void_p), len(e), _ptr(rows), int(n_rows), int(csum),
+            _ptr(out), _stream(stream, self.device)), "ingot_gpu_parse_modify_rows")
+        del keep
         return out
 
     def parse_read_modify(self, arena, seg_off, seg_len, pkt_seg, chain: Chain, edits,

@@ -347,6 +347,60 @@ def edits_array(edits) -> np.ndarray:
     return a
 
 
+class WideField(enum.IntEnum):
+    """enum ingot_wide_field: the 6- and 16-byte setter targets, valid only in
+    ingot_edit_rows (ingot_gpu_parse_modify_rows)."""
+
+    ETH_DESTINATION = 64
+    ETH_SOURCE = 65
+    V6_SOURCE = 66
+    V6_DESTINATION = 67
+
+
+WIDE_BYTES = {WideField.ETH_DESTINATION: 6, WideField.ETH_SOURCE: 6, WideField.V6_SOURCE: 16,
+              WideField.V6_DESTINATION: 16}
+
+
+class EditSource(enum.IntEnum):
+    """enum ingot_edit_source: where an ingot_edit_rows operand comes from."""
+
+    VALUE = 0  # `value`, the same for every packet
+    U16 = 1    # a host-endian u16 per row (device table)
+    U32 = 2    # a host-endian u32 per row (device table)
+    BYTES = 3  # a wide field's 6 or 16 bytes in wire order per row (device table)
+
+
+class EditBy(enum.IntEnum):
+    """enum ingot_edit_by: which row of its table packet i takes."""
+
+    PACKET = 0  # row i
+    ROW = 1     # row d_row[i]
+
+
+ROW_NONE = 0xFFFFFFFF
+
+
+class IngotEditRows(ctypes.Structure):
+    _fields_ = [("layer", U8), ("field", U8), ("op", U8), ("index", U8), ("value", U32),
+                ("source", U8), ("by", U8), ("_pad", U16), ("pitch", U32),
+                ("d_values", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(IngotEditRows) == 24
+EDIT_ROWS_DTYPE = np.dtype(IngotEditRows)
+
+
+def edit_rows_array(rows) -> np.ndarray:
+    """[(layer, field, op, index, value, source, by, pitch, values pointer), ...]
+    -> ingot_edit_rows array."""
+    a = np.zeros(len(rows), dtype=EDIT_ROWS_DTYPE)
+    for k, e in enumerate(rows):
+        for name, v in zip(("layer", "field", "op", "index", "value", "source", "by", "pitch",
+                            "d_values"), e):
+            a[k][name] = int(v)
+    return a
+
+
 class EmitSource(enum.IntEnum):
     """enum ingot_emit_source: where a per-packet setter's value comes from."""
 

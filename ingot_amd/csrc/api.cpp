@@ -707,6 +707,117 @@ int modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off, const ui
                          : ingot_gpu::launch_modify(a, layout, chain, t, (hipStream_t)stream));
 }
 
+// ingot_gpu_parse_modify_rows: the sums a wide field's bytes feed.  IPv6
+// addresses: the L4 sum's pseudo-header at the parsed L3 layer (FEED_PSEUDO4's
+// run-time condition, TCP / UDP / ICMPv6, is the IPv6 pseudo-header's too),
+// the tunnel's outer sum as its pseudo-header (layer 1) or as covered bytes
+// (layer 5).  MACs: the tunnel's inner Ethernet (layer 4) is covered by the
+// outer sum; layer 0 feeds nothing.
+int wide_feeds(int chain, const ingot_edit_rows& e, uint32_t what) {
+    using namespace ingot_gpu;
+    const bool tun = chain == INGOT_CHAIN_GENEVE_OVER_V6;
+    const bool v6 = e.field == INGOT_FW_V6_SOURCE || e.field == INGOT_FW_V6_DESTINATION;
+    uint32_t f = 0;
+    if (v6 && (!tun || e.layer == 5) && (what & INGOT_CSUM_L4)) f |= FEED_PSEUDO4;
+    if (tun && (what & INGOT_CSUM_OUTER_L4) && (v6 ? e.layer == 1 || e.layer == 5 : e.layer == 4))
+        f |= FEED_OUTER;
+    return (int)f;
+}
+
+// ingot_gpu_parse_modify_rows: every argument is checked before any device
+// work, in the order the header gives.
+int modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off,
+                const uint16_t* d_len, uint32_t stride, uint64_t n, int chain,
+                const ingot_edit_rows* edits, uint32_t n_edits, const uint32_t* d_row,
+                uint32_t n_rows, uint32_t what, ingot_rec* d_out, void* stream) {
+    using namespace ingot_gpu;
+    if (!ctx || !chain_ok(chain) || n_edits > INGOT_MAX_EDITS || (n_edits && !edits))
+        return INGOT_GPU_EINVAL;
+    ModifyRowsArgs a{};
+    uint32_t np = 0;
+    for (uint32_t k = 0; k < n_edits; ++k) {
+        const ingot_edit_rows& e = edits[k];
+        const bool wide = e.field >= INGOT_FW_ETH_DESTINATION && e.field <= INGOT_FW_V6_DESTINATION;
+        if ((!wide && e.field >= INGOT_F_COUNT) || e.op > INGOT_OP_XOR ||
+            (int)e.layer >= ingot_chain_layer_count(chain))
+            return INGOT_GPU_EINVAL;
+        if (e.source > INGOT_EDIT_BYTES || e.by > INGOT_BY_ROW || e._pad) return INGOT_GPU_EINVAL;
+        const bool table = e.source != INGOT_EDIT_VALUE;
+        if (table && (e.value || !e.d_values)) return INGOT_GPU_EINVAL;
+        if ((e.source == INGOT_EDIT_BYTES) != wide) return INGOT_GPU_EINVAL;
+        if (wide && e.op != INGOT_OP_SET) return INGOT_GPU_EINVAL;
+        const bool mac = e.field == INGOT_FW_ETH_DESTINATION || e.field == INGOT_FW_ETH_SOURCE;
+        const uint32_t width = e.source == INGOT_EDIT_U16   ? 2u
+                               : e.source == INGOT_EDIT_U32 ? 4u
+                               : wide                       ? (mac ? 6u : 16u)
+                                                            : 0u;
+        if (e.pitch && e.pitch < width) return INGOT_GPU_EINVAL;
+        if ((e.source == INGOT_EDIT_U16 || e.source == INGOT_EDIT_U32) &&
+            (((uintptr_t)e.d_values | e.pitch) & (width - 1u)))
+            return INGOT_GPU_EINVAL;
+        if (e.by == INGOT_BY_ROW && !d_row) return INGOT_GPU_EINVAL;
+        const uint32_t pitch = e.pitch ? e.pitch : width;
+        if (!wide) {
+            const FieldGeo g = kFieldGeo[e.field];
+            RowPiece& d = a.e[np++];
+            d.e = Edit{e.layer, g.kind, e.op, e.index, (uint8_t)(g.bit / 8u),
+                       (uint8_t)((g.bit % 8u + g.bits + 7u) / 8u),
+                       (uint8_t)((8u - ((g.bit + g.bits) % 8u)) % 8u), g.bits, e.value};
+            d.source = e.source;  // VALUE / U16 / U32 are RowSource's first three
+            d.by = e.by;
+            d.pitch = pitch;
+            d.values = static_cast<const uint8_t*>(e.d_values);
+            continue;
+        }
+        // a wide field: big-endian SET pieces of 4 (and, a MAC's last, 2) bytes
+        const uint32_t at = mac ? (e.field == INGOT_FW_ETH_SOURCE ? 6u : 0u)
+                                : (e.field == INGOT_FW_V6_DESTINATION ? 24u : 8u);
+        for (uint32_t b = 0; b < width; b += 4u) {
+            const uint32_t nb = width - b < 4u ? width - b : 4u;
+            RowPiece& d = a.e[np++];
+            d.e = Edit{e.layer, (uint8_t)(mac ? HK_ETH : HK_V6), INGOT_OP_SET, e.index,
+                       (uint8_t)(at + b), (uint8_t)nb, 0, (uint8_t)(8u * nb), 0u};
+            d.source = nb == 4u ? ROWS_BE32 : ROWS_BE16;
+            d.by = e.by;
+            d.pitch = pitch;
+            d.values = static_cast<const uint8_t*>(e.d_values) + b;
+        }
+    }
+    a.n_pieces = np;
+    if ((what & ~(INGOT_CSUM_L3 | INGOT_CSUM_L4 | INGOT_CSUM_OUTER_L4)) ||
+        ((what & INGOT_CSUM_OUTER_L4) && chain != INGOT_CHAIN_GENEVE_OVER_V6))
+        return INGOT_GPU_EINVAL;
+    if (what) {
+        np = 0;
+        for (uint32_t k = 0; k < n_edits; ++k) {
+            const ingot_edit_rows& e = edits[k];
+            const bool wide = e.field >= INGOT_FW_ETH_DESTINATION;
+            const int f = wide ? wide_feeds(chain, e, what)
+                               : csum_feeds(chain, ingot_edit{e.layer, e.field, e.op, e.index, 0u},
+                                            what);
+            if (f < 0) return INGOT_GPU_EINVAL;
+            const uint32_t pieces = !wide ? 1u : e.field <= INGOT_FW_ETH_SOURCE ? 2u : 4u;
+            for (uint32_t j = 0; j < pieces; ++j) a.e[np++].feeds = (uint8_t)f;
+        }
+    }
+    if (n == 0) return INGOT_GPU_SUCCESS;
+    if (!d_arena) return INGOT_GPU_EINVAL;
+    int layout = LAYOUT_INDEXED;
+    if (!d_off) {
+        if (int e = stride_ok(d_arena, stride)) return e;
+        layout = LAYOUT_STRIDED;
+    } else if (!d_len) {
+        return INGOT_GPU_EINVAL;
+    }
+    if (int e = enter(ctx)) return e;
+    a.p = ParseArgs{d_arena, d_off, d_len, stride, n, d_out};
+    a.row = d_row;
+    a.n_rows = n_rows;
+    a.what = what;
+    return from_hip(launch_modify_rows(a, layout, chain, tuning_for(ctx, d_arena),
+                                       (hipStream_t)stream));
+}
+
 // ingot_gpu_parse_read_modify (what == 0) and ingot_gpu_parse_read_modify_csum:
 // the same edit list over parse_read's CSR chunk tables.
 int read_modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_seg_off,
@@ -743,6 +854,15 @@ int ingot_gpu_parse_modify_csum(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint
     if (!csum_what_ok(what, chain)) return INGOT_GPU_EINVAL;
     return modify(ctx, d_arena, d_off, d_len, stride, n, chain, edits, n_edits, what, d_out,
                   stream);
+}
+
+int ingot_gpu_parse_modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off,
+                                const uint16_t* d_len, uint32_t stride, uint64_t n, int chain,
+                                const ingot_edit_rows* edits, uint32_t n_edits,
+                                const uint32_t* d_row, uint32_t n_rows, uint32_t what,
+                                ingot_rec* d_out, void* stream) {
+    return modify_rows(ctx, d_arena, d_off, d_len, stride, n, chain, edits, n_edits, d_row,
+                       n_rows, what, d_out, stream);
 }
 
 int ingot_gpu_parse_read_modify(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_seg_off,

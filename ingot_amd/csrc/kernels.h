@@ -95,6 +95,39 @@ struct ModifyCsumArgs {
 // (the fixed L4 header), by the L4 sum's IPv4 pseudo-header (the addresses:
 // fed only when the packet's L4 layer has one) or by the tunnel's outer UDP sum.
 enum CsumFeed : uint8_t { FEED_L3 = 1, FEED_L4 = 2, FEED_OUTER = 4, FEED_PSEUDO4 = 8 };
+// ingot_gpu_parse_modify_rows: per-packet operands.  api.cpp resolves each
+// ingot_edit_rows to one piece (a narrow field) or to 4-byte SET pieces (an
+// IPv6 address: 4; a MAC: a 4-byte and a 2-byte one), each an Edit of at most
+// 4 bytes for the shared apply_edit, with where its operand comes from.  A
+// block of its own, so the ModifyArgs / ModifyCsumArgs kernels keep theirs.
+enum RowSource : uint8_t {
+    ROWS_VALUE = 0,  // e.value
+    ROWS_U16 = 1,    // host-endian u16 at the row (aligned)
+    ROWS_U32 = 2,    // host-endian u32 at the row (aligned)
+    ROWS_BE16 = 3,   // 2 bytes of the row, big-endian (any alignment)
+    ROWS_BE32 = 4    // 4 bytes of the row, big-endian (any alignment)
+};
+struct RowPiece {
+    Edit e;                 // e.value: the operand of a ROWS_VALUE piece
+    uint8_t source;         // RowSource
+    uint8_t by;             // INGOT_BY_PACKET / INGOT_BY_ROW
+    uint8_t feeds;          // CsumFeed bits
+    uint8_t _pad;
+    uint32_t pitch;         // bytes between rows
+    const uint8_t* values;  // the table + the piece's byte offset in its row
+};
+constexpr uint32_t ROWS_MAX_PIECES = 4 * INGOT_MAX_EDITS;
+struct ModifyRowsArgs {
+    ParseArgs p;
+    const uint32_t* row;  // optional: per-packet row index (the row guard)
+    uint32_t n_rows;
+    uint32_t what;        // INGOT_CSUM_* bits, or 0
+    uint32_t n_pieces;
+    RowPiece e[ROWS_MAX_PIECES];
+};
+static_assert(sizeof(RowPiece) == 32, "RowPiece is 32 bytes");
+static_assert(sizeof(ModifyRowsArgs) <= 4096,
+              "ModifyRowsArgs exceeds the 4 KiB kernel-argument limit");
 // 3,824 B today (ParseArgs + key windows + the 16-bit table): the kernarg
 // segment is 4 KiB, and a larger FlowArgs would fail flow launches at run
 // time, not here.
@@ -285,6 +318,10 @@ hipError_t launch_modify(const ModifyArgs& a, int layout_kind, int chain, const 
 hipError_t launch_modify_ring_csum(const ModifyCsumArgs& a, int chain, const Tuning& t,
                                    hipStream_t s);
 hipError_t launch_modify_csum(const ModifyCsumArgs& a, int layout_kind, int chain,
+                              const Tuning& t, hipStream_t s);
+// The rewrite with per-packet operands (ingot_gpu_parse_modify_rows): k_parse's
+// OUT_MODIFY kernels only, never the slot-ring kernel.
+hipError_t launch_modify_rows(const ModifyRowsArgs& a, int layout_kind, int chain,
                               const Tuning& t, hipStream_t s);
 // The rewrite over parse_read's chunk tables (ingot_gpu_parse_read_modify[_csum],
 // read.hip): `a.p` holds the CSR tables as LAYOUT_SEGMENTED does, out and chunk

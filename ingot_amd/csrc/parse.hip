@@ -34,9 +34,13 @@ namespace {
 
 // ARGS = ModifyCsumArgs (OUT_MODIFY only): the fused checksum update after the
 // edits (ingot_gpu_parse_modify_csum; walk.h: csum_finish).
+// ARGS = ModifyRowsArgs (OUT_MODIFY only): each piece's operand from a device
+// table, by packet or by the packet's row, behind the row guard, and the same
+// checksum update (ingot_gpu_parse_modify_rows; walk.h: row_operand).
 template <uint32_t NCH, int LAYOUT, int CHAIN, int MODE, class ARGS>
 __global__ __launch_bounds__(BLOCK) void k_parse(ARGS args) {
-    constexpr bool CSUM = std::is_same<ARGS, ModifyCsumArgs>::value;
+    constexpr bool ROWS = std::is_same<ARGS, ModifyRowsArgs>::value;
+    constexpr bool CSUM = std::is_same<ARGS, ModifyCsumArgs>::value || ROWS;
     static_assert(!CSUM || MODE == OUT_MODIFY, "checksums are updated by the rewrite only");
     const ParseArgs& a = base_args(args);
     constexpr bool TUN = CHAIN == INGOT_CHAIN_GENEVE_OVER_V6;
@@ -179,20 +183,43 @@ __global__ __launch_bounds__(BLOCK) void k_parse(ARGS args) {
             // parse, then the setters in order (each sees the previous
             // edits' bytes: staged ones in the window, whose sectors may be
             // written back only after the loop, the others in HBM)
+            // the packet's row, loaded before the walk so that the gather of
+            // its table rows does not wait for two dependent round trips
+            [[maybe_unused]] uint32_t row = 0;
+            bool edit = valid;
+            if constexpr (ROWS) {
+                if (valid && args.row) {
+                    row = args.row[i];
+                    edit = row < args.n_rows;  // the row guard: INGOT_ROW_NONE too
+                }
+            }
             walk<CHAIN, false>(fr, r, nullptr, nullptr);
-            if (valid && r.status == INGOT_OK) {
+            if (edit && r.status == INGOT_OK) {
                 EditSink sink{const_cast<uint8_t*>(a.arena) + off, off, base, len, NCH ? nch : 0u,
                               0u, mis};
                 [[maybe_unused]] typename std::conditional<CSUM, CsumAcc, NoCsum>::type acc;
-                const ModifyArgs& m = edit_args(args);
-                for (uint32_t k = 0; k < m.n_edits; ++k) {
-                    const Edit e = m.e[k];
-                    uint32_t h;
-                    if (header_at<CHAIN>(r, e.layer, e.kind, e.index, h)) {
-                        if constexpr (CSUM)
-                            csum_feed(acc, args.feeds[k], r, apply_edit<true>(fr, sink, h, e));
-                        else
-                            apply_edit(fr, sink, h, e);
+                if constexpr (ROWS) {
+                    for (uint32_t k = 0; k < args.n_pieces; ++k) {
+                        const RowPiece& pc = args.e[k];
+                        Edit e = pc.e;
+                        uint32_t h;
+                        // (no table is read for a piece that is not applied)
+                        if (header_at<CHAIN>(r, e.layer, e.kind, e.index, h)) {
+                            e.value = row_operand(pc, pc.by == INGOT_BY_ROW ? (uint64_t)row : i);
+                            csum_feed(acc, pc.feeds, r, apply_edit<true>(fr, sink, h, e));
+                        }
+                    }
+                } else {
+                    const ModifyArgs& m = edit_args(args);
+                    for (uint32_t k = 0; k < m.n_edits; ++k) {
+                        const Edit e = m.e[k];
+                        uint32_t h;
+                        if (header_at<CHAIN>(r, e.layer, e.kind, e.index, h)) {
+                            if constexpr (CSUM)
+                                csum_feed(acc, args.feeds[k], r, apply_edit<true>(fr, sink, h, e));
+                            else
+                                apply_edit(fr, sink, h, e);
+                        }
                     }
                 }
                 // the two checksum bytes go through the edits' sink, so the
@@ -392,6 +419,22 @@ hipError_t launch_modify(const ModifyArgs& a, int layout_kind, int chain, const 
 hipError_t launch_modify_csum(const ModifyCsumArgs& a, int layout_kind, int chain,
                               const Tuning& t, hipStream_t s) {
     return launch_modify_as(a, layout_kind, chain, t, s);
+}
+
+// Per-packet operands: launch_modify_as's k_parse windows for every layout;
+// slot rings too (k_modify_pipe has no table loads).
+hipError_t launch_modify_rows(const ModifyRowsArgs& a, int layout_kind, int chain,
+                              const Tuning& t, hipStream_t s) {
+    if (a.p.n == 0) return hipSuccess;
+    const uint32_t g = grid_for(a.p.n, t.max_blocks);
+    const bool tun = chain == INGOT_CHAIN_GENEVE_OVER_V6;
+    if (layout_kind == LAYOUT_STRIDED) {
+        if (tun) return launch_chain<8, LAYOUT_STRIDED, OUT_MODIFY>(a, chain, g, s);
+        return a.p.stride <= 64u ? launch_chain<4, LAYOUT_STRIDED, OUT_MODIFY>(a, chain, g, s)
+                                 : launch_chain<3, LAYOUT_STRIDED, OUT_MODIFY>(a, chain, g, s);
+    }
+    return tun ? launch_chain<8, LAYOUT_INDEXED, OUT_MODIFY>(a, chain, g, s)
+               : launch_chain<3, LAYOUT_INDEXED, OUT_MODIFY>(a, chain, g, s);
 }
 
 // Flow mode needs the addresses (IPv6: 32 bytes past byte 22) and ports, so

@@ -929,6 +929,7 @@ __device__ __forceinline__ const ParseArgs& base_args(const ParseArgs& a) { retu
 __device__ __forceinline__ const ParseArgs& base_args(const FlowArgs& a) { return a.p; }
 __device__ __forceinline__ const ParseArgs& base_args(const ModifyArgs& a) { return a.p; }
 __device__ __forceinline__ const ParseArgs& base_args(const ModifyCsumArgs& a) { return a.m.p; }
+__device__ __forceinline__ const ParseArgs& base_args(const ModifyRowsArgs& a) { return a.p; }
 // the rewrite's edit list, with or without the checksum update's extras
 __host__ __device__ __forceinline__ const ModifyArgs& edit_args(const ModifyArgs& a) { return a; }
 __host__ __device__ __forceinline__ const ModifyArgs& edit_args(const ModifyCsumArgs& a) {
@@ -1122,6 +1123,25 @@ __device__ __forceinline__ uint32_t apply_edit(const FR& f, EditSink& sink, uint
         put_byte(f, sink, h + e.byte0 + k, (uint8_t)(w >> (8u * (e.nbytes - 1u - k))));
     if constexpr (CSUM) return csum_term(h + e.byte0, e.nbytes, w_old, (uint32_t)w);
     else return 0u;
+}
+
+// The operand of one piece of ingot_gpu_parse_modify_rows for row `r` of its
+// table (the packet's index or its d_row entry): a per-lane global load,
+// coalesced by packet, a gather by row.  U16 / U32 rows are aligned (api.cpp
+// checks the table and the pitch); byte rows may sit at any address, so their
+// big-endian pieces are assembled from bytes unless the piece is 4-B aligned.
+__device__ __forceinline__ uint32_t row_operand(const RowPiece& pc, uint64_t r) {
+    if (pc.source == ROWS_VALUE) return pc.e.value;
+    const uint8_t* p = pc.values + r * pc.pitch;
+    switch (pc.source) {
+    case ROWS_U16: return *reinterpret_cast<const uint16_t*>(p);
+    case ROWS_U32: return *reinterpret_cast<const uint32_t*>(p);
+    case ROWS_BE16: return ((uint32_t)p[0] << 8) | p[1];
+    default:
+        if (((uintptr_t)p & 3u) == 0u)
+            return __builtin_bswap32(*reinterpret_cast<const uint32_t*>(p));
+        return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
+    }
 }
 
 // RSS Toeplitz over one 32-bit input word (MSB first) whose first bit is
