@@ -41,7 +41,8 @@ extern "C" {
 /* 4: ingot_gpu_checksum_verify / ingot_gpu_checksum_fill (ingot_csum);
  *    ingot_gpu_parse_modify_csum, ingot_gpu_checksum_verify_read / _fill_read,
  *    ingot_gpu_parse_read_modify / ingot_gpu_parse_read_modify_csum,
- *    ingot_gpu_parse_modify_rows (added calls: the number stays).
+ *    ingot_gpu_parse_modify_rows, ingot_gpu_flow_table_* /
+ *    ingot_gpu_flow_key_hash (added calls: the number stays).
  * 3: ingot_gpu_comm_wrap (borrow the host's RCCL communicator).
  * 2: ingot_gpu_comm_* / ingot_gpu_flow_hist_allreduce (config 5's reduce);
  *    host mappings counted per map, ingot_gpu_host_unmap EINVAL for a pointer
@@ -1415,6 +1416,75 @@ int ingot_gpu_flow_hist_ws(ingot_gpu_ctx* ctx, const uint8_t* d_arena,
                            uint32_t* d_hash, uint32_t* d_hist, void* d_work,
                            size_t work_bytes, void* stream);
 size_t ingot_gpu_flow_hist_workspace_size(uint64_t n, uint32_t bins);
+
+/* ---------------------------------------------------------------------------
+ * Exact-match flow table, host side: the 40-byte per-packet flow key and a
+ * table from keys to action-table rows (build-defined, like the flow hash:
+ * ingot has no flow table; tests/flow_lookup_model.py is the definition of the
+ * key and of the lookup).  ingot_gpu_flow_hist's bins collide, so two flows in
+ * one bin share a row of a bins-row table; an exact-match table gives every
+ * flow its own row for ingot_gpu_parse_modify_rows (d_row, n_rows = the action
+ * table's size).  This is the host half: the key, the table's layout and hash,
+ * build / insert / find.  The device calls that fill d_row from it are not in
+ * the library yet.
+ *
+ * The key, 40 bytes.  w[0..8] are the nine words ingot_gpu_flow_hist hashes:
+ * source address, destination address, then the L4 header's first word
+ * (source port | destination port) when the L4 layer is TCP or UDP, else 0;
+ * IPv4 fills words 0-2, IPv6 words 0-8, the rest are zero.  Each word is the
+ * host-endian value of the big-endian read (10.0.0.1 is 0x0a000001).
+ * w[9] = (l3_kind << 8) | l4_proto; its upper 16 bits are zero (reserved).
+ * A packet has a key exactly when ingot_gpu_flow_hist counts it: its record
+ * is Ok and l3_kind != NONE; the layers are the ones the record describes
+ * (the tunnel chain's inner layers once INGOT_REC_INNER is set).  A packet
+ * without a key has 40 zero bytes: w[9] == 0 belongs to no key, and marks an
+ * empty slot of the table.
+ *
+ * The table (host side: no context, no GPU).  A caller-owned buffer of
+ * ingot_gpu_flow_table_bytes(slots) = 64 * (slots + 1) bytes, `slots` a power
+ * of two in [MIN_SLOTS, MAX_SLOTS] (0 for any other `slots`); the layout is
+ * opaque.  Open addressing, linear probing from
+ * ingot_gpu_flow_key_hash(key) & (slots - 1), wrapping.
+ *   _build   zeroes the buffer, then inserts keys[i] -> rows[i] in order
+ *            (n_keys may be 0; keys / rows may then be NULL).
+ *   _insert  one key on a host copy: a key already present has its row
+ *            replaced (the last one wins, the count stays).  INGOT_GPU_ERANGE,
+ *            the table left as it was, when the count would exceed slots / 2
+ *            or the key would land MAX_PROBE or more slots from its home:
+ *            double `slots` and rebuild.  (_build stops at the first such key.)
+ *   _find    the key's row, or INGOT_ROW_NONE (also for any bad argument); at
+ *            most MAX_PROBE slots are probed, stopping at an empty one.
+ *   _key_hash  the hash (0 for NULL), so hosts can reason about home slots.
+ * INGOT_GPU_EINVAL: `slots` not a power of two in range; table_bytes !=
+ * 64 * (slots + 1); a NULL table, or NULL key / keys / rows where one is
+ * needed; a key whose w[9] >> 8 is not 1 or 2 (upper bits non-zero included);
+ * a row equal to INGOT_ROW_NONE; _insert / _find on a buffer whose header
+ * does not match table_bytes.
+ * The buffer is made to be uploaded whole to 64-B-aligned device memory: one
+ * slot is one aligned 64-B read.
+ *
+ * Out of scope: the device-side key extraction and lookup (see above);
+ * removal (rebuild the table); a VNI-qualified key (w[9]'s upper bits are
+ * reserved for it); the C++ mirror ingot_amd.hpp.
+ * ------------------------------------------------------------------------- */
+typedef struct ingot_flow_key { uint32_t w[10]; } ingot_flow_key;
+
+#ifdef __cplusplus
+static_assert(sizeof(ingot_flow_key) == 40, "ingot_flow_key is 40 bytes");
+#endif
+
+#define INGOT_FLOW_TABLE_MIN_SLOTS 16u
+#define INGOT_FLOW_TABLE_MAX_SLOTS (1u << 26)
+#define INGOT_FLOW_TABLE_MAX_PROBE 128u
+size_t ingot_gpu_flow_table_bytes(uint32_t slots);
+int ingot_gpu_flow_table_build(const ingot_flow_key* keys, const uint32_t* rows,
+                               uint32_t n_keys, uint32_t slots, void* table,
+                               size_t table_bytes);
+int ingot_gpu_flow_table_insert(void* table, size_t table_bytes,
+                                const ingot_flow_key* key, uint32_t row);
+uint32_t ingot_gpu_flow_table_find(const void* table, size_t table_bytes,
+                                   const ingot_flow_key* key);
+uint32_t ingot_gpu_flow_key_hash(const ingot_flow_key* key);
 
 /*
  * The multi-GPU reduce of config 5 (the only collective of the design).

@@ -32,6 +32,11 @@ from .abi import (  # noqa: F401  (re-exports)
     IngotCsum,
     FIELDS_BYTES,
     FIELDS_DTYPE,
+    FLOW_KEY_BYTES,
+    FLOW_KEY_DTYPE,
+    FLOW_TABLE_MAX_PROBE,
+    FLOW_TABLE_MAX_SLOTS,
+    FLOW_TABLE_MIN_SLOTS,
     GEN_SEED,
     GENEVE_FIELDS_DTYPE,
     MAX_GENEVE_OPT_FIELDS,
@@ -75,7 +80,8 @@ __all__ = [
     "GenericUlp", "VlanUlp", "GeneveOverV6Tunnel", "gen_frames", "gen_lengths", "records_to_numpy",
     "fields_to_numpy", "load_library", "Parsed", "chunk_tables", "HeaderKind", "parse_header",
     "HeaderParseError", "first_chunks", "CsumState", "CSUM_L3", "CSUM_L4", "CSUM_OUTER_L4",
-    "CSUM_DTYPE", "EmitSum",
+    "CSUM_DTYPE", "EmitSum", "FLOW_KEY_DTYPE", "flow_table_bytes", "flow_table_build",
+    "flow_table_insert", "flow_table_find", "flow_key_hash",
 ]
 
 
@@ -852,6 +858,97 @@ class Context:
         if not b:
             return None
         return _torch().empty(b, dtype=_torch().uint8, device=f"cuda:{self.device}")
+
+
+def _flow_keys_np(keys):
+    """Keys as a contiguous (m, 10) uint32 array: FLOW_KEY_DTYPE records,
+    (m, 10) / (10,) words or (m, 40) bytes."""
+    import numpy as np
+
+    a = np.ascontiguousarray(keys)
+    if a.dtype == FLOW_KEY_DTYPE:
+        a = a.view("<u4")
+    elif a.dtype == np.uint8:
+        a = a.reshape(-1, FLOW_KEY_BYTES).view("<u4")
+    a = np.ascontiguousarray(a, dtype=np.uint32).reshape(-1, 10)
+    return a
+
+
+def _one_flow_key(keys) -> bool:
+    """One key rather than a batch: a FLOW_KEY_DTYPE scalar, or a 1-d array of
+    its 10 words or 40 bytes."""
+    import numpy as np
+
+    a = np.asarray(keys)
+    return a.ndim == 0 if a.dtype == FLOW_KEY_DTYPE else a.ndim == 1
+
+
+def flow_table_bytes(slots: int) -> int:
+    """Bytes of a flow table of `slots` slots (ingot_gpu_flow_table_bytes);
+    0 unless slots is a power of two in [MIN_SLOTS, MAX_SLOTS]."""
+    if not 0 <= int(slots) <= 0xFFFFFFFF:
+        return 0
+    return int(_lib.load().ingot_gpu_flow_table_bytes(int(slots)))
+
+
+def flow_table_build(keys, rows, slots: int):
+    """A flow table on the host (ingot_gpu_flow_table_build): keys[i] ->
+    rows[i], inserted in order, in a new uint8 numpy array whose data is 64-B
+    aligned, as the device side will want it uploaded."""
+    import numpy as np
+
+    k = _flow_keys_np(keys)
+    r = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1)
+    if len(k) != len(r):
+        raise ValueError("keys and rows must have the same length")
+    nbytes = flow_table_bytes(slots)
+    if not nbytes:
+        raise ValueError("slots must be a power of two in [FLOW_TABLE_MIN_SLOTS, "
+                         "FLOW_TABLE_MAX_SLOTS]")
+    raw = np.empty(nbytes + 64, dtype=np.uint8)
+    skip = -raw.ctypes.data % 64
+    table = raw[skip:skip + nbytes]
+    _lib.check(_lib.load().ingot_gpu_flow_table_build(k.ctypes.data, r.ctypes.data, len(k),
+                                                      int(slots), table.ctypes.data, nbytes),
+               "ingot_gpu_flow_table_build")
+    return table
+
+
+def flow_table_insert(table, key, row: int) -> None:
+    """Add key -> row to a host table in place (ingot_gpu_flow_table_insert);
+    a key already present has its row replaced.  Raises when the table is
+    half full or the probe chain too long: build a table of twice the slots."""
+    k = _flow_keys_np(key)
+    if len(k) != 1:
+        raise ValueError("one key")
+    _lib.check(_lib.load().ingot_gpu_flow_table_insert(table.ctypes.data, table.nbytes,
+                                                       k.ctypes.data, int(row)),
+               "ingot_gpu_flow_table_insert")
+
+
+def flow_table_find(table, keys):
+    """Rows of `keys` in a host table (ingot_gpu_flow_table_find): one int for
+    one key, else a uint32 array; ROW_NONE for an absent key."""
+    import numpy as np
+
+    k = _flow_keys_np(keys)
+    find = _lib.load().ingot_gpu_flow_table_find
+    tp, tb, kp = table.ctypes.data, table.nbytes, k.ctypes.data
+    out = np.fromiter((find(tp, tb, kp + 40 * i) for i in range(len(k))), dtype=np.uint32,
+                      count=len(k))
+    return int(out[0]) if _one_flow_key(keys) else out
+
+
+def flow_key_hash(keys):
+    """The table's hash of `keys` (ingot_gpu_flow_key_hash): home slot =
+    hash & (slots - 1).  One int for one key, else a uint32 array."""
+    import numpy as np
+
+    k = _flow_keys_np(keys)
+    h = _lib.load().ingot_gpu_flow_key_hash
+    out = np.fromiter((h(k.ctypes.data + 40 * i) for i in range(len(k))), dtype=np.uint32,
+                      count=len(k))
+    return int(out[0]) if _one_flow_key(keys) else out
 
 
 def first_chunks(seg_off, seg_len, pkt_seg):

@@ -177,6 +177,18 @@ SIGNATURES = {
          ctypes.c_uint32, c_u8p, c_u8p, c_u8p, c_u8p, ctypes.c_size_t, ctypes.c_void_p],
     ),
     "ingot_gpu_flow_hist_workspace_size": (ctypes.c_size_t, [c_u64, ctypes.c_uint32]),
+    "ingot_gpu_flow_table_bytes": (ctypes.c_size_t, [ctypes.c_uint32]),
+    "ingot_gpu_flow_table_build": (
+        ctypes.c_int,
+        [c_u8p, c_u8p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t],
+    ),
+    "ingot_gpu_flow_table_insert": (
+        ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, c_u8p, ctypes.c_uint32],
+    ),
+    "ingot_gpu_flow_table_find": (
+        ctypes.c_uint32, [ctypes.c_void_p, ctypes.c_size_t, c_u8p],
+    ),
+    "ingot_gpu_flow_key_hash": (ctypes.c_uint32, [c_u8p]),
     "ingot_gpu_comm_unique_id": (ctypes.c_int, [ctypes.c_void_p]),
     "ingot_gpu_comm_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),

@@ -390,6 +390,15 @@ assert ctypes.sizeof(IngotEditRows) == 24
 EDIT_ROWS_DTYPE = np.dtype(IngotEditRows)
 
 
+# ingot_flow_key: the nine hash input words, then (l3_kind << 8) | l4_proto
+FLOW_KEY_DTYPE = np.dtype([("w", "<u4", (10,))])
+assert FLOW_KEY_DTYPE.itemsize == 40
+FLOW_KEY_BYTES = FLOW_KEY_DTYPE.itemsize
+FLOW_TABLE_MIN_SLOTS = 16       # INGOT_FLOW_TABLE_MIN_SLOTS
+FLOW_TABLE_MAX_SLOTS = 1 << 26  # INGOT_FLOW_TABLE_MAX_SLOTS
+FLOW_TABLE_MAX_PROBE = 128      # INGOT_FLOW_TABLE_MAX_PROBE
+
+
 def edit_rows_array(rows) -> np.ndarray:
     """[(layer, field, op, index, value, source, by, pitch, values pointer), ...]
     -> ingot_edit_rows array."""
