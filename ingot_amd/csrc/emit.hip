@@ -75,11 +75,6 @@ struct WaveDesc {
     uint32_t _pad[WAVE - 6];
 };
 
-// Per-packet LDS of the UDP sum: the packet's accumulator and the one or two
-// chunks that hold the checksum field (two when its bytes straddle a 16-B
-// destination boundary), parked until the sum is known.
-constexpr uint32_t SUM_LDS_PER_PACKET = 4u + 2u * 16u;
-
 template <bool COPY, bool SUMS = false>
 __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
     static_assert(COPY || !SUMS, "sums need the payload: whole packets only");
@@ -88,15 +83,8 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
     constexpr uint32_t NPOW = NP <= 64 ? 64 : NP <= 128 ? 128 : 256;  // search span
     using Desc = WaveDesc<NP>;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    // the header block between zero bytes, as 16-B blocks
     u32x4* tmpl = reinterpret_cast<u32x4*>(smem);
-    constexpr uint32_t TB = INGOT_MAX_EMIT_HDR / 16 + 4;  // 16 B before, 48 B after
-    for (uint32_t k = threadIdx.x; k < TB; k += BLOCK) {
-        const bool in = k >= 1 && k <= INGOT_MAX_EMIT_HDR / 16;
-        tmpl[k] = in ? u32x4{a.hdr[4 * k - 4], a.hdr[4 * k - 3], a.hdr[4 * k - 2],
-                             a.hdr[4 * k - 1]}
-                     : u32x4{0u, 0u, 0u, 0u};
-    }
+    load_template(tmpl, a, BLOCK);
     const uint32_t H = a.hdr_len;
     const uint32_t RS = region_bytes(H);
     const uint32_t lane = threadIdx.x % WAVE, g = threadIdx.x / (W * WAVE);
@@ -119,10 +107,6 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
         const uint32_t L = live ? (uint32_t)gbl(a.len)[i] : 0u;
         const uint64_t doff = live ? (a.dst_off ? gbl(a.dst_off)[i] : i * (uint64_t)a.stride) : 0u;
         const uint64_t soff = (COPY && live) ? gbl(a.off)[i] : 0u;
-        uint32_t v[INGOT_MAX_EMIT_SETS];
-#pragma unroll
-        for (uint32_t s = 0; s < INGOT_MAX_EMIT_SETS; ++s)
-            v[s] = (s < a.n_sets && live) ? set_value(a.sets[s], i, H + L) : 0u;
         uint8_t* D = a.dst + doff;
         const uint8_t* S = COPY ? a.src + soff : nullptr;
         const uint32_t T = H + (COPY ? L : 0u);
@@ -130,70 +114,13 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
         const uint32_t s_mis = COPY ? (uint32_t)((uintptr_t)(S - H - dmis) & 15u) : 0u;
         const uint32_t nch = live ? (dmis + T + 15u) / 16u : 0u;
 
-        // 2. the packet's header block in its region: template bytes shifted to
-        //    the destination's alignment (region byte b = header byte b - dmis),
-        //    then the setters byte by byte (neighbouring bits kept)
+        // 2. the packet's header block in its region, and (2b) its sums' start
         uint8_t* R = regions + j * RS;
-        if (H && live) {
-            for (uint32_t m = 0; m < RS / 16u; ++m) {
-                const uint32_t tb = 16u + 16u * m - dmis;  // template byte of region byte 16m (+16)
-                reinterpret_cast<u32x4*>(R)[m] = funnel(tmpl[tb >> 4], tmpl[(tb >> 4) + 1], tb & 15u);
-            }
-#pragma unroll
-            for (uint32_t s = 0; s < INGOT_MAX_EMIT_SETS; ++s) {
-                if (s >= a.n_sets) break;
-                const EmitSet& e = a.sets[s];
-                const uint32_t fm = e.bits >= 32 ? 0xffffffffu : ((1u << e.bits) - 1u);
-                const uint32_t m = fm << e.rshift, vb = (v[s] & fm) << e.rshift;
-                for (uint32_t k = 0; k < e.nbytes; ++k) {
-                    const uint32_t shb = 8u * (e.nbytes - 1u - k);
-                    uint8_t& b = R[dmis + e.pos + k];
-                    b = (uint8_t)((b & ~(m >> shb)) | ((vb >> shb) & (m >> shb)));
-                }
-            }
-        }
-
-        if constexpr (SUMS) {
-            // 2b. the sums of what this lane just patched.  IPv4: complete, and
-            //     written into the region before anything reads it (so a UDP
-            //     segment that covers the header sums the final bytes).  UDP:
-            //     the header bytes of the segment [udp_at, H) without the
-            //     field, and the pseudo-header, start the packet's accumulator;
-            //     the walkers add the payload.  All of it has the parity of
-            //     the destination address (`at` and `l3_at` are even).
-            const uint32_t odd = dmis & 1u;
-            if (live && a.sums.v4) {
-                const uint32_t b0 = dmis + a.sums.v4_at;
-                R[b0 + 10] = 0;
-                R[b0 + 11] = 0;
-                const uint32_t f = fold16(region_words(R, b0, b0 + a.sums.v4_len));
-                const uint32_t c = ~(odd ? f : swap16(f)) & 0xffffu;
-                R[b0 + 10] = (uint8_t)(c >> 8);
-                R[b0 + 11] = (uint8_t)c;
-            }
-            if (a.sums.udp) {
-                uint32_t s = 0;
-                if (live) {
-                    const uint32_t b0 = dmis + a.sums.udp_at, l3 = dmis + a.sums.udp_l3;
-                    const uint32_t seg = H + L - a.sums.udp_at;  // > 65535: never written
-                    const uint32_t tail = fold16(seg + 17u);     // length and next header / protocol
-                    s = region_words(R, b0, dmis + H) - ((uint32_t)R[b0 + 6] << (8u * odd)) -
-                        ((uint32_t)R[b0 + 7] << (8u * (odd ^ 1u))) +
-                        (a.sums.udp_v6 ? region_words(R, l3 + 8u, l3 + 40u)
-                                       : region_words(R, l3 + 12u, l3 + 20u)) +
-                        (odd ? tail : swap16(tail));
-                }
-                acc[j] = s;
-            }
-        }
+        build_region(R, RS, tmpl, a, i, live, dmis, H + L);
+        if constexpr (SUMS) start_sums(R, a, live, dmis, H + L, acc + j);
 
         // 3. chunk counts -> inclusive prefix over the wave
-        uint32_t P = nch;
-#pragma unroll
-        for (uint32_t o = 1; o < WAVE; o <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)P, o);
-            if (lane >= o) P += y;
-        }
+        const uint32_t P = wave_inclusive_sum(nch, lane);
         wd.dst[j] = (uint64_t)(uintptr_t)D;
         wd.src[j] = (uint64_t)(uintptr_t)S;
         wd.pfx[j] = P;
@@ -297,81 +224,27 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
                 n2.w = from_next_lane(own[u].w);
                 out = funnel(own[u], extra[u] ? nb[u] : n2, qs);
             }
-            if (H && valid && r0 < (int32_t)H) {
-                const u32x4 hb = *reinterpret_cast<const u32x4*>(regions + qq * RS + 16u * c[u]);
-                const int32_t hc = (int32_t)H - r0;
-                const uint32_t m0 = head_mask(hc, 0), m1 = head_mask(hc, 1),
-                               m2 = head_mask(hc, 2), m3 = head_mask(hc, 3);
-                out.x = (hb.x & m0) | (out.x & ~m0);
-                out.y = (hb.y & m1) | (out.y & ~m1);
-                out.z = (hb.z & m2) | (out.z & ~m2);
-                out.w = (hb.w & m3) | (out.w & ~m3);
-            }
+            if (H && valid && r0 < (int32_t)H)
+                merge_header(out, *reinterpret_cast<const u32x4*>(regions + qq * RS + 16u * c[u]),
+                             H, r0);
             bool parked = false;
             if constexpr (SUMS) {
-                if (udp) {
-                    // the payload bytes of this chunk, [p0, p1): their words as
-                    // loaded; a segmented inclusive scan over the wave (the
-                    // lanes of a packet are contiguous, chunk c[u] is c[u]
-                    // lanes after its packet's first) leaves the packet's share
-                    // of this step in its last lane, which adds it in LDS
-                    const int32_t p0 = max((int32_t)H - r0, 0), p1 = min((int32_t)QT - r0, 16);
-                    uint32_t s = (valid && p0 < p1) ? chunk_words(out, p0, p1) : 0u;
-#pragma unroll
-                    for (uint32_t o = 1; o < WAVE; o <<= 1) {
-                        const uint32_t y = (uint32_t)__shfl_up((int)s, o);
-                        if (lane >= o && o <= c[u]) s += y;
-                    }
-                    if (last[u] && s) atomicAdd(&acc[qq], s);
-                    // the chunk(s) holding the field wait in LDS for the sum
-                    const uint32_t cf = (qd + fpos) >> 4;
-                    parked = valid && (c[u] == cf || c[u] == ((qd + fpos + 1u) >> 4));
-                    if (parked) park[(c[u] - cf) * NP + qq] = out;
-                }
+                if (udp)
+                    parked = udp_share(out, valid, last[u], c[u], qq, qd, H, QT, r0, fpos, lane,
+                                       acc, park, NP);
             }
-            if (valid && !parked) {
-                const int32_t t0 = r0 < 0 ? -r0 : 0;
-                const int32_t t1 = (int32_t)QT - r0 < 16 ? (int32_t)QT - r0 : 16;
-                if (t0 == 0 && t1 == 16) {
-                    *(__attribute__((address_space(1))) u32x4*)(QD + r0) = out;
-                } else {
-                    store_edge(QD + r0, out, t0, t1);
-                }
-            }
+            if (valid && !parked) store_chunk(QD, r0, QT, out);
         }
     }
     if constexpr (SUMS) {
         if (!udp) return;
-        // 5. every chunk is summed once the block is here.  One lane per parked
-        //    chunk: fold the packet's sum, put the field's byte(s) that lie in
-        //    this chunk, and issue the chunk's only store.
+        // 5. the parked chunks, once the block has summed every chunk
         __syncthreads();
-        if (threadIdx.x >= 2u * NP) return;
         const uint32_t slot = threadIdx.x / NP, j = threadIdx.x % NP;
-        if (base + j >= a.n) return;
-        const uint32_t qd = wd.mis[j] & 0xffu;
-        const uint32_t cf = (qd + fpos) >> 4;
-        if (slot && ((qd + fpos + 1u) >> 4) == cf) return;  // the field sits in one chunk
-        const uint32_t c = cf + slot;
-        u32x4 out = park[slot * NP + j];
-        const uint32_t QT = H + wd.len[j];
-        if (QT - a.sums.udp_at <= 65535u) {
-            const uint32_t f = fold16(acc[j]);
-            uint32_t sum = ~((qd & 1u) ? f : swap16(f)) & 0xffffu;
-            sum = sum ? sum : 0xffffu;
-            const int32_t pos = (int32_t)(qd + fpos) - (int32_t)(16u * c);
-            put_byte(out, pos, sum >> 8);
-            put_byte(out, pos + 1, sum & 0xffu);
-        }
-        uint8_t* QD = (uint8_t*)(uintptr_t)wd.dst[j];
-        const int32_t r0 = (int32_t)(16u * c) - (int32_t)qd;
-        const int32_t t0 = r0 < 0 ? -r0 : 0;
-        const int32_t t1 = (int32_t)QT - r0 < 16 ? (int32_t)QT - r0 : 16;
-        if (t0 == 0 && t1 == 16) {
-            *(__attribute__((address_space(1))) u32x4*)(QD + r0) = out;
-        } else {
-            store_edge(QD + r0, out, t0, t1);
-        }
+        if (slot >= 2u || base + j >= a.n) return;
+        finish_parked(a, fpos, slot, wd.mis[j] & 0xffu, H + wd.len[j],
+                      (uint8_t*)(uintptr_t)wd.dst[j],
+                      park + slot * NP + j, acc + j);
     }
 }
 

@@ -1,28 +1,20 @@
-// emit_common.h — device helpers shared by the emit kernels (emit.hip: k_emit;
-// emit_read.hip: k_emit_read): the funnel shift and its DPP neighbour, the
-// predicated edge store, the header / byte masks, the setters' values and the
-// 16-bit word sums of the fused checksums.  One copy of each.
+// emit_common.h — what the emit kernels share (emit.hip: k_emit; emit_read.hip:
+// k_emit_read).  Helpers: the funnel shift and its DPP neighbour, the
+// predicated edge store, the setters' values, the 16-bit word sums of the
+// fused checksums (sums.h).  Steps of the kernels, below them: the template
+// load, a packet's region and the start of its sums, and a destination
+// chunk's way out (header merge, UDP share, store, the parked chunks' finish).
+// One copy of each; the kernels keep their descriptors and how a chunk's
+// payload bytes are loaded.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "../../include/ingot_gpu.h"
 #include "kernels.h"
+#include "sums.h"
 
 namespace ingot_gpu {
 namespace {
-
-constexpr uint32_t WAVE = 64;
-
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-template <class T>
-__device__ __forceinline__ const __attribute__((address_space(1))) T* gbl(const T* p) {
-    return (const __attribute__((address_space(1))) T*)p;
-}
-template <class T>
-__device__ __forceinline__ __attribute__((address_space(1))) T* gbl_mut(T* p) {
-    return (__attribute__((address_space(1))) T*)p;
-}
 
 // The 16 bytes at byte s (0..15, per lane) of the 32-B pair a ++ b: rotate
 // by whole dwords in two select stages (2, then 1), then v_alignbyte.
@@ -40,12 +32,6 @@ __device__ __forceinline__ u32x4 funnel(const u32x4& a, const u32x4& b, uint32_t
 // The value of the next lane (lane 63: 0): DPP wave_shl:1, no LDS traffic.
 __device__ __forceinline__ uint32_t from_next_lane(uint32_t x) {
     return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x130, 0xf, 0xf, true);
-}
-
-__device__ __forceinline__ uint32_t head_mask(int32_t hc, uint32_t d) {
-    // bytes [4d, 4d+4) of a chunk whose first hc bytes are header bytes
-    const int32_t k = hc - (int32_t)(4u * d);
-    return k >= 4 ? 0xffffffffu : k <= 0 ? 0u : ((1u << (8u * (uint32_t)k)) - 1u);
 }
 
 __device__ __forceinline__ uint32_t set_value(const EmitSet& e, uint64_t i, uint32_t total) {
@@ -100,26 +86,8 @@ __device__ __forceinline__ void store_edge(uint8_t* p, const u32x4& v, int32_t t
     }
 }
 
-// --- ingot_gpu_emit_packets_csum (the SUMS instantiation) -------------------
-// Sums are kept as the 16-bit words of aligned dwords added as loaded (the
-// sum is byte-order independent); a segment's big-endian sum is the folded
-// value, byte-swapped unless the segment starts at an odd address.
-__device__ __forceinline__ uint32_t fold16(uint32_t x) {
-    x = (x & 0xffffu) + (x >> 16);
-    return (x & 0xffffu) + (x >> 16);
-}
-__device__ __forceinline__ uint32_t swap16(uint32_t x) { return ((x & 0xffu) << 8) | (x >> 8); }
-__device__ __forceinline__ uint32_t below(int32_t k) {  // bytes [0, k) of a dword, k any integer
-    return k >= 4 ? 0xffffffffu : k <= 0 ? 0u : ((1u << (8u * (uint32_t)k)) - 1u);
-}
-// Bytes [b0, b1) of a 16-B chunk: its 16-bit words as loaded, added.
-__device__ __forceinline__ uint32_t chunk_words(const u32x4& v, int32_t b0, int32_t b1) {
-    const uint32_t x = v.x & below(b1) & ~below(b0), y = v.y & below(b1 - 4) & ~below(b0 - 4),
-                   z = v.z & below(b1 - 8) & ~below(b0 - 8), w = v.w & below(b1 - 12) & ~below(b0 - 12);
-    return (x & 0xffffu) + (x >> 16) + (y & 0xffffu) + (y >> 16) + (z & 0xffffu) + (z >> 16) +
-           (w & 0xffffu) + (w >> 16);
-}
-// The same over bytes [b0, b1) of a packet's region (LDS, 16-B aligned).
+// --- ingot_gpu_emit_packets_csum (the SUMS instantiations; sums.h has the words) ---
+// The 16-bit words as loaded of bytes [b0, b1) of a packet's region (LDS, 16-B aligned), added.
 __device__ __forceinline__ uint32_t region_words(const uint8_t* R, uint32_t b0, uint32_t b1) {
     uint32_t s = 0;
     for (uint32_t d = b0 >> 2; 4u * d < b1; ++d) {
@@ -139,6 +107,160 @@ __device__ __forceinline__ void put_byte(u32x4& v, int32_t pos, uint32_t val) {
     v.y = d == 1 ? (v.y & ~m) | b : v.y;
     v.z = d == 2 ? (v.z & ~m) | b : v.z;
     v.w = d == 3 ? (v.w & ~m) | b : v.w;
+}
+
+// --- the kernels' shared steps ----------------------------------------------
+// Per-packet LDS of the UDP sum: the packet's accumulator and the one or two
+// chunks that hold the checksum field (two when its bytes straddle a 16-B
+// destination boundary), parked until the sum is known.
+constexpr uint32_t SUM_LDS_PER_PACKET = 4u + 2u * 16u;
+
+// The header block between zero bytes, as TB 16-B blocks at the start of LDS.
+constexpr uint32_t TB = INGOT_MAX_EMIT_HDR / 16 + 4;  // 16 B before, 48 B after
+__device__ __forceinline__ void load_template(u32x4* tmpl, const EmitArgs& a, uint32_t block) {
+    for (uint32_t k = threadIdx.x; k < TB; k += block) {
+        const bool in = k >= 1 && k <= INGOT_MAX_EMIT_HDR / 16;
+        tmpl[k] = in ? u32x4{a.hdr[4 * k - 4], a.hdr[4 * k - 3], a.hdr[4 * k - 2],
+                             a.hdr[4 * k - 1]}
+                     : u32x4{0u, 0u, 0u, 0u};
+    }
+}
+
+// Step 2.  Packet i's header block in its region R (RS bytes of LDS): the
+// template bytes shifted to the destination's alignment (region byte b =
+// header byte b - dmis), then the setters byte by byte: every covering byte's
+// new value depends only on its own mask and value bits (neighbouring bits
+// kept).  `total` is what INGOT_EMIT_LENGTH counts from.
+__device__ __forceinline__ void build_region(uint8_t* R, uint32_t RS, const u32x4* tmpl,
+                                             const EmitArgs& a, uint64_t i, bool live,
+                                             uint32_t dmis, uint32_t total) {
+    uint32_t v[INGOT_MAX_EMIT_SETS];  // coalesced set-value loads
+#pragma unroll
+    for (uint32_t s = 0; s < INGOT_MAX_EMIT_SETS; ++s)
+        v[s] = (s < a.n_sets && live) ? set_value(a.sets[s], i, total) : 0u;
+    if (!a.hdr_len || !live) return;
+    for (uint32_t m = 0; m < RS / 16u; ++m) {
+        const uint32_t tb = 16u + 16u * m - dmis;  // template byte of region byte 16m (+16)
+        reinterpret_cast<u32x4*>(R)[m] = funnel(tmpl[tb >> 4], tmpl[(tb >> 4) + 1], tb & 15u);
+    }
+#pragma unroll
+    for (uint32_t s = 0; s < INGOT_MAX_EMIT_SETS; ++s) {
+        if (s >= a.n_sets) break;
+        const EmitSet& e = a.sets[s];
+        const uint32_t fm = e.bits >= 32 ? 0xffffffffu : ((1u << e.bits) - 1u);
+        const uint32_t m = fm << e.rshift, vb = (v[s] & fm) << e.rshift;
+        for (uint32_t k = 0; k < e.nbytes; ++k) {
+            const uint32_t shb = 8u * (e.nbytes - 1u - k);
+            uint8_t& b = R[dmis + e.pos + k];
+            b = (uint8_t)((b & ~(m >> shb)) | ((vb >> shb) & (m >> shb)));
+        }
+    }
+}
+
+// Step 2b.  The sums of the region its lane just patched (`total` = header +
+// payload bytes).  IPv4: complete, and written into the region before
+// anything reads it (so a UDP segment that covers the header sums the final
+// bytes).  UDP: the header bytes of the segment [udp_at, H) without the
+// field, and the pseudo-header, start the packet's accumulator *acc; the
+// walkers add the payload.  All of it has the parity of the destination
+// address (`at` and `l3_at` are even).
+__device__ __forceinline__ void start_sums(uint8_t* R, const EmitArgs& a, bool live,
+                                           uint32_t dmis, uint32_t total, uint32_t* acc) {
+    const uint32_t odd = dmis & 1u;
+    if (live && a.sums.v4) {
+        const uint32_t b0 = dmis + a.sums.v4_at;
+        R[b0 + 10] = 0;
+        R[b0 + 11] = 0;
+        const uint32_t f = fold16(region_words(R, b0, b0 + a.sums.v4_len));
+        const uint32_t c = ~(odd ? f : swap16(f)) & 0xffffu;
+        R[b0 + 10] = (uint8_t)(c >> 8);
+        R[b0 + 11] = (uint8_t)c;
+    }
+    if (a.sums.udp) {
+        uint32_t s = 0;
+        if (live) {
+            const uint32_t b0 = dmis + a.sums.udp_at, l3 = dmis + a.sums.udp_l3;
+            const uint32_t seg = total - a.sums.udp_at;  // > 65535: never written
+            const uint32_t tail = fold16(seg + 17u);     // length and next header / protocol
+            s = region_words(R, b0, dmis + a.hdr_len) - ((uint32_t)R[b0 + 6] << (8u * odd)) -
+                ((uint32_t)R[b0 + 7] << (8u * (odd ^ 1u))) +
+                (a.sums.udp_v6 ? region_words(R, l3 + 8u, l3 + 40u)
+                               : region_words(R, l3 + 12u, l3 + 20u)) +
+                (odd ? tail : swap16(tail));
+        }
+        *acc = s;
+    }
+}
+
+// A destination chunk whose byte 0 is packet byte r0: its first H - r0 bytes
+// are header bytes and come from the packet's region (hb: the region's chunk,
+// by value: a pointer here moved the kernels' LDS load).
+__device__ __forceinline__ void merge_header(u32x4& out, const u32x4 hb, uint32_t H, int32_t r0) {
+    const int32_t hc = (int32_t)H - r0;
+    const uint32_t m0 = below(hc), m1 = below(hc - 4), m2 = below(hc - 8), m3 = below(hc - 12);
+    out.x = (hb.x & m0) | (out.x & ~m0);
+    out.y = (hb.y & m1) | (out.y & ~m1);
+    out.z = (hb.z & m2) | (out.z & ~m2);
+    out.w = (hb.w & m3) | (out.w & ~m3);
+}
+
+// The UDP share of chunk c of packet qq (destination misalignment qd, QT
+// bytes, the checksum field at header byte fpos): the words as loaded of its
+// payload bytes; a segmented inclusive scan over the wave (the lanes of a
+// packet are contiguous, chunk c is c lanes after its packet's first) leaves
+// the packet's share of this step in its last lane (`last`), which adds it in
+// LDS.  The chunk(s) holding the field wait in `park` (two slots of np
+// chunks) for the sum: returns whether this one does.
+__device__ __forceinline__ bool udp_share(const u32x4& out, bool valid, bool last, uint32_t c,
+                                          uint32_t qq, uint32_t qd, uint32_t H, uint32_t QT,
+                                          int32_t r0, uint32_t fpos, uint32_t lane, uint32_t* acc,
+                                          u32x4* park, uint32_t np) {
+    const int32_t p0 = max((int32_t)H - r0, 0), p1 = min((int32_t)QT - r0, 16);
+    uint32_t s = (valid && p0 < p1) ? chunk_words(out, p0, p1) : 0u;
+#pragma unroll
+    for (uint32_t o = 1; o < WAVE; o <<= 1) {
+        const uint32_t y = (uint32_t)__shfl_up((int)s, o);
+        if (lane >= o && o <= c) s += y;
+    }
+    if (last && s) atomicAdd(&acc[qq], s);
+    const uint32_t cf = (qd + fpos) >> 4;
+    const bool parked = valid && (c == cf || c == ((qd + fpos + 1u) >> 4));
+    if (parked) park[(c - cf) * np + qq] = out;
+    return parked;
+}
+
+// The chunk whose byte 0 is byte r0 of the QT-byte packet at QD: whole as one
+// 16-B store, a packet's first or last chunk as predicated pieces.
+__device__ __forceinline__ void store_chunk(uint8_t* QD, int32_t r0, uint32_t QT, const u32x4 out) {
+    const int32_t t0 = r0 < 0 ? -r0 : 0;
+    const int32_t t1 = (int32_t)QT - r0 < 16 ? (int32_t)QT - r0 : 16;
+    if (t0 == 0 && t1 == 16) {
+        *(__attribute__((address_space(1))) u32x4*)(QD + r0) = out;
+    } else {
+        store_edge(QD + r0, out, t0, t1);
+    }
+}
+
+// Step 5, once every chunk of the group is summed: one lane per parked chunk
+// (`slot` 0 / 1 of the packet at QD, misalignment qd, QT bytes) folds the
+// packet's sum, puts the field's byte(s) that lie in this chunk, and issues
+// the chunk's only store.
+__device__ __forceinline__ void finish_parked(const EmitArgs& a, uint32_t fpos, uint32_t slot,
+                                              uint32_t qd, uint32_t QT, uint8_t* QD,
+                                              const u32x4* parked, const uint32_t* acc) {
+    const uint32_t cf = (qd + fpos) >> 4;
+    if (slot && ((qd + fpos + 1u) >> 4) == cf) return;  // the field sits in one chunk
+    const uint32_t c = cf + slot;
+    u32x4 out = *parked;
+    if (QT - a.sums.udp_at <= 65535u) {
+        const uint32_t f = fold16(*acc);
+        uint32_t sum = ~((qd & 1u) ? f : swap16(f)) & 0xffffu;
+        sum = sum ? sum : 0xffffu;
+        const int32_t pos = (int32_t)(qd + fpos) - (int32_t)(16u * c);
+        put_byte(out, pos, sum >> 8);
+        put_byte(out, pos + 1, sum & 0xffu);
+    }
+    store_chunk(QD, (int32_t)(16u * c) - (int32_t)qd, QT, out);
 }
 
 }  // namespace

@@ -3,13 +3,11 @@
 //
 // The source of packet i is the chunk list of ingot_gpu_parse_read, cut at
 // 65,535 logical bytes, of which the bytes [f, f + t) are the payload (d_from /
-// d_take, clamped).  The destination side is k_emit's (emit.hip): the header
-// block patched per packet in an LDS region at the destination's 16-B
-// alignment, the group's packets as one flat run of aligned 16-B destination
-// blocks that the group's 16 waves take in turns, whole blocks stored whole,
-// the two edge blocks of a packet as predicated pieces (store_edge), the UDP
-// sum accumulated from the finished blocks in destination coordinates and the
-// block(s) holding its field parked until the group's barrier.
+// d_take, clamped).  The destination side is k_emit's (emit.hip), through the
+// steps both kernels call in emit_common.h: start_sums per packet (and
+// build_region's body, see step 2), then per aligned 16-B destination block
+// of the group's flat run merge_header, udp_share and store_chunk, and
+// finish_parked behind the group's barrier.  Everything about the sum is in destination coordinates.
 //
 // What differs is where a block's payload bytes come from.  A *piece* is the
 // part of one non-empty chunk that lies inside the payload; in payload
@@ -61,8 +59,6 @@ struct ReadDesc {
     uint32_t sub[4];             // blocks of each 64-packet subgroup
     uint32_t _pad[WAVE - 4];
 };
-
-constexpr uint32_t SUM_LDS_PER_PACKET = 4u + 2u * 16u;  // as k_emit: accumulator + two parked blocks
 
 struct Piece {
     uint64_t sbase;
@@ -117,15 +113,8 @@ template <bool SUMS>
 __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_emit_read(EmitReadArgs ar) {
     const EmitArgs& a = ar.e;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    // the header block between zero bytes, as 16-B blocks
     u32x4* tmpl = reinterpret_cast<u32x4*>(smem);
-    constexpr uint32_t TB = INGOT_MAX_EMIT_HDR / 16 + 4;  // 16 B before, 48 B after
-    for (uint32_t k = threadIdx.x; k < TB; k += BLOCK) {
-        const bool in = k >= 1 && k <= INGOT_MAX_EMIT_HDR / 16;
-        tmpl[k] = in ? u32x4{a.hdr[4 * k - 4], a.hdr[4 * k - 3], a.hdr[4 * k - 2],
-                             a.hdr[4 * k - 1]}
-                     : u32x4{0u, 0u, 0u, 0u};
-    }
+    load_template(tmpl, a, BLOCK);
     const uint32_t H = a.hdr_len;
     const uint32_t RS = region_bytes(H);
     const uint32_t lane = threadIdx.x % WAVE;
@@ -184,9 +173,12 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_
         const uint32_t dmis = (uint32_t)((uintptr_t)D & 15u);
         const uint32_t nch = live ? (dmis + T + 15u) / 16u : 0u;
 
-        // 2. the packet's header block in its region, as k_emit's step 2:
-        //    template bytes shifted to the destination's alignment (region byte
-        //    b = header byte b - dmis), then the setters byte by byte
+        // 2. the packet's header block in its region: build_region's body
+        //    (emit_common.h), kept here with the set values loaded before the
+        //    destination is: called as a function it is the only shared step
+        //    that changes this kernel's code, and the two-chunk copy without
+        //    sums then measured 0.3 % slower
+        //    (profiles/r18_csum_emit_shared_ab.json).  (2b) its sums' start
         uint8_t* R = regions + j * RS;
         if (H && live) {
             for (uint32_t m = 0; m < RS / 16u; ++m) {
@@ -206,46 +198,10 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_
                 }
             }
         }
-
-        if constexpr (SUMS) {
-            // 2b. as k_emit's step 2b.  IPv4: complete, written into the region
-            //     before anything reads it.  UDP: the header bytes of the
-            //     segment without the field, and the pseudo-header, start the
-            //     packet's accumulator; the walkers add the payload.  All of it
-            //     has the parity of the destination address.
-            const uint32_t odd = dmis & 1u;
-            if (live && a.sums.v4) {
-                const uint32_t b0 = dmis + a.sums.v4_at;
-                R[b0 + 10] = 0;
-                R[b0 + 11] = 0;
-                const uint32_t fs = fold16(region_words(R, b0, b0 + a.sums.v4_len));
-                const uint32_t c = ~(odd ? fs : swap16(fs)) & 0xffffu;
-                R[b0 + 10] = (uint8_t)(c >> 8);
-                R[b0 + 11] = (uint8_t)c;
-            }
-            if (a.sums.udp) {
-                uint32_t s = 0;
-                if (live) {
-                    const uint32_t b0 = dmis + a.sums.udp_at, l3 = dmis + a.sums.udp_l3;
-                    const uint32_t seg = H + L - a.sums.udp_at;  // > 65535: never written
-                    const uint32_t tail = fold16(seg + 17u);     // length and next header / protocol
-                    s = region_words(R, b0, dmis + H) - ((uint32_t)R[b0 + 6] << (8u * odd)) -
-                        ((uint32_t)R[b0 + 7] << (8u * (odd ^ 1u))) +
-                        (a.sums.udp_v6 ? region_words(R, l3 + 8u, l3 + 40u)
-                                       : region_words(R, l3 + 12u, l3 + 20u)) +
-                        (odd ? tail : swap16(tail));
-                }
-                acc[j] = s;
-            }
-        }
+        if constexpr (SUMS) start_sums(R, a, live, dmis, T, acc + j);
 
         // 3. block counts -> inclusive prefix over the wave
-        uint32_t P = nch;
-#pragma unroll
-        for (uint32_t o = 1; o < WAVE; o <<= 1) {
-            const uint32_t y = (uint32_t)__shfl_up((int)P, o);
-            if (lane >= o) P += y;
-        }
+        const uint32_t P = wave_inclusive_sum(nch, lane);
         wd.dst[j] = (uint64_t)(uintptr_t)D;
         wd.pfx[j] = P;
         wd.len[j] = L;
@@ -360,79 +316,26 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_
             n2.z = from_next_lane(own[u].z);
             n2.w = from_next_lane(own[u].w);
             u32x4 out = funnel(own[u], (fl[u] & 16u) ? nb[u] : n2, fl[u] & 15u);
-            if (H && valid && r0 < (int32_t)H) {
-                const u32x4 hb = *reinterpret_cast<const u32x4*>(regions + qq * RS + 16u * c[u]);
-                const int32_t hc = (int32_t)H - r0;
-                const uint32_t m0 = head_mask(hc, 0), m1 = head_mask(hc, 1),
-                               m2 = head_mask(hc, 2), m3 = head_mask(hc, 3);
-                out.x = (hb.x & m0) | (out.x & ~m0);
-                out.y = (hb.y & m1) | (out.y & ~m1);
-                out.z = (hb.z & m2) | (out.z & ~m2);
-                out.w = (hb.w & m3) | (out.w & ~m3);
-            }
+            if (H && valid && r0 < (int32_t)H)
+                merge_header(out, *reinterpret_cast<const u32x4*>(regions + qq * RS + 16u * c[u]),
+                             H, r0);
             bool parked = false;
             if constexpr (SUMS) {
-                if (udp) {
-                    // as k_emit: the payload bytes of this block, a segmented
-                    // inclusive scan over the wave, the packet's share of this
-                    // step added in LDS by its last lane
-                    const int32_t p0 = max((int32_t)H - r0, 0), p1 = min((int32_t)QT - r0, 16);
-                    uint32_t s = (valid && p0 < p1) ? chunk_words(out, p0, p1) : 0u;
-#pragma unroll
-                    for (uint32_t o = 1; o < WAVE; o <<= 1) {
-                        const uint32_t y = (uint32_t)__shfl_up((int)s, o);
-                        if (lane >= o && o <= c[u]) s += y;
-                    }
-                    if ((fl[u] & 32u) && s) atomicAdd(&acc[qq], s);
-                    // the block(s) holding the field wait in LDS for the sum
-                    const uint32_t cf = (qd + fpos) >> 4;
-                    parked = valid && (c[u] == cf || c[u] == ((qd + fpos + 1u) >> 4));
-                    if (parked) park[(c[u] - cf) * NP + qq] = out;
-                }
+                if (udp)
+                    parked = udp_share(out, valid, fl[u] & 32u, c[u], qq, qd, H, QT, r0, fpos, lane,
+                                       acc, park, NP);
             }
-            if (valid && !parked) {
-                const int32_t t0 = r0 < 0 ? -r0 : 0;
-                const int32_t t1 = (int32_t)QT - r0 < 16 ? (int32_t)QT - r0 : 16;
-                if (t0 == 0 && t1 == 16) {
-                    *(__attribute__((address_space(1))) u32x4*)(QD + r0) = out;
-                } else {
-                    store_edge(QD + r0, out, t0, t1);
-                }
-            }
+            if (valid && !parked) store_chunk(QD, r0, QT, out);
         }
     }
     if constexpr (SUMS) {
         if (!udp) return;
-        // 5. every block is summed once the group is here.  One lane per parked
-        //    block: fold the packet's sum, put the field's byte(s) that lie in
-        //    this block, and issue the block's only store.
+        // 5. the parked blocks, once the group has summed every block
         __syncthreads();
-        if (threadIdx.x >= 2u * NP) return;
         const uint32_t slot = threadIdx.x / NP, j = threadIdx.x % NP;
-        if (base + j >= a.n) return;
-        const uint32_t qd = wd.dmis[j];
-        const uint32_t cf = (qd + fpos) >> 4;
-        if (slot && ((qd + fpos + 1u) >> 4) == cf) return;  // the field sits in one block
-        const uint32_t c = cf + slot;
-        u32x4 out = park[slot * NP + j];
-        const uint32_t QT = H + wd.len[j];
-        if (QT - a.sums.udp_at <= 65535u) {
-            const uint32_t f = fold16(acc[j]);
-            uint32_t sum = ~((qd & 1u) ? f : swap16(f)) & 0xffffu;
-            sum = sum ? sum : 0xffffu;
-            const int32_t pos = (int32_t)(qd + fpos) - (int32_t)(16u * c);
-            put_byte(out, pos, sum >> 8);
-            put_byte(out, pos + 1, sum & 0xffu);
-        }
-        uint8_t* QD = (uint8_t*)(uintptr_t)wd.dst[j];
-        const int32_t r0 = (int32_t)(16u * c) - (int32_t)qd;
-        const int32_t t0 = r0 < 0 ? -r0 : 0;
-        const int32_t t1 = (int32_t)QT - r0 < 16 ? (int32_t)QT - r0 : 16;
-        if (t0 == 0 && t1 == 16) {
-            *(__attribute__((address_space(1))) u32x4*)(QD + r0) = out;
-        } else {
-            store_edge(QD + r0, out, t0, t1);
-        }
+        if (slot >= 2u || base + j >= a.n) return;
+        finish_parked(a, fpos, slot, wd.dmis[j], H + wd.len[j], (uint8_t*)(uintptr_t)wd.dst[j],
+                      park + slot * NP + j, acc + j);
     }
 }
 

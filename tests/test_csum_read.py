@@ -401,6 +401,42 @@ def test_adversarial_frames_split_anywhere(ctx, torch):
 
 
 # ---------------------------------------------------------------------------
+# one chunk per packet: the contiguous kernel's answer
+# ---------------------------------------------------------------------------
+@pytest.mark.parametrize("mis", [0, 1, 15])
+def test_one_chunk_per_packet_is_the_contiguous_call(ctx, torch, mis):
+    """k_csum and k_csum_read share their header decode, block reduction and
+    finish (csum.hip).  257 MIXED frames (a full group and one packet), the
+    arena copied to byte misalignment `mis`, every packet one chunk, the same
+    records for both: checksum_verify_read's rows are checksum_verify's, and
+    checksum_fill_read leaves checksum_fill's rows and arena bytes."""
+    n = GROUP + 1
+    arena, off, lens = gen_frames_host(GenProfile.MIXED, n, seed=257, slack=64)
+    recs = oracle.parse_batch(arena, off, lens, Chain.GenericUlp)
+    moved = np.full(len(arena) + 16, 0xA5, np.uint8)
+    moved[mis:mis + len(arena)] = arena
+    d_off, d_len = _dev(torch, off + np.uint64(mis)), _dev(torch, lens)
+    d_ps = _dev(torch, np.arange(n + 1, dtype=np.uint32))
+    d_rec = _dev(torch, recs).view(-1, 16)
+    d_a = _dev(torch, moved)
+    assert d_a.data_ptr() % 16 == 0
+    flat = _rows(ctx.checksum_verify(d_a, d_off, d_len, d_rec))
+    _same_rows(_rows(ctx.checksum_verify_read(d_a, d_off, d_len, d_ps, d_rec)), flat, "verify")
+    assert d_a.cpu().numpy().tobytes() == moved.tobytes()
+    assert (flat["l4_len"] > 0).sum() > n // 2 and (flat["l3_state"] != NONE).sum() > n // 4
+    d_b = d_a.clone()
+    rows_a = torch.zeros((n, 8), dtype=torch.uint8, device="cuda")
+    rows_b = torch.zeros((n, 8), dtype=torch.uint8, device="cuda")
+    ctx.checksum_fill(d_a, d_off, d_len, d_rec, out=rows_a)
+    ctx.checksum_fill_read(d_b, d_off, d_len, d_ps, d_rec, out=rows_b)
+    _same_rows(_rows(rows_b), _rows(rows_a), "fill")
+    got_a, got_b = d_a.cpu().numpy(), d_b.cpu().numpy()
+    bad = np.nonzero(got_a != got_b)[0]
+    assert bad.size == 0, ("arena after fill", bad[:10], got_a[bad[:10]], got_b[bad[:10]])
+    assert (got_a != moved).sum() > n // 2  # the fill wrote
+
+
+# ---------------------------------------------------------------------------
 # aliased payload, the encapsulation, arguments, streams
 # ---------------------------------------------------------------------------
 def test_aliased_payload_chunk(ctx, torch):

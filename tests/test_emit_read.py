@@ -293,6 +293,36 @@ def test_no_sums_and_one_chunk(ctx, torch):
     _same(got, old(hdr, sets, sums, src, off, ln, dst_off, size), "emit_packets_csum")
 
 
+@pytest.mark.parametrize("name", ["opte", "geneve_v4"])
+def test_one_chunk_per_packet_is_emit_packets_csum(ctx, torch, name):
+    """k_emit and k_emit_read share every step but the payload load
+    (emit_common.h).  257 MIXED generator frames (a full group and one
+    packet), every packet one chunk, no from / take, the stack's sums (`opte`:
+    the UDP sum over IPv6; `geneve_v4`: the IPv4 and the UDP sum), the
+    destinations at misalignments 0, 1 and 15: the two calls write identical
+    bytes.  (emit_packets with `sums` is ingot_gpu_emit_packets_csum.)"""
+    n = NP + 1
+    src, off, lens = gen_frames_host(GenProfile.MIXED, n, seed=257, slack=64)
+    hdr, sets, sums = cases.stack(name, n, np.random.default_rng(18))
+    d_sets = _dev_sets(torch, sets)
+    d_src, d_off, d_len = _dev(torch, src), _dev(torch, off), _dev(torch, lens)
+    d_ps = _dev(torch, np.arange(n + 1, dtype=np.uint32))
+    for dmis in (0, 1, 15):
+        dst_off, size = _slots(n, len(hdr) + int(lens.max()), np.full(n, dmis))
+        d_dst_off = _dev(torch, dst_off)
+        d_old = _dev(torch, np.full(size, 0xA5, np.uint8))
+        d_new = d_old.clone()
+        assert d_old.data_ptr() % 16 == 0 and d_new.data_ptr() % 16 == 0
+        ctx.emit_packets(hdr, d_sets, d_src, d_off, d_len, d_old, d_dst_off, sums=sums)
+        ctx.emit_packets_read(hdr, d_sets, d_src, d_off, d_len, d_ps, d_new, d_dst_off, sums=sums)
+        old, new = d_old.cpu().numpy(), d_new.cpu().numpy()
+        _same(new, old, (name, dmis))
+        for i in (0, NP - 1, NP):  # the payload is there, behind the header block
+            o = int(dst_off[i]) + len(hdr)
+            assert new[o:o + int(lens[i])].tobytes() == \
+                src[int(off[i]):int(off[i]) + int(lens[i])].tobytes(), (name, dmis, i)
+
+
 def test_aliased_payload_and_streams(ctx, torch):
     """64 packets share one payload chunk behind their own header chunks; the
     same on a side stream."""

@@ -30,7 +30,11 @@ interleaved rounds, beside c3_verify as the yardstick:
 Their algorithmic bytes are the checksum's with 10 B per chunk and 4 B per
 packet of tables in place of the 10 B of packed descriptors.
 
-    python tools/csum_probe.py [--frames N] [--reps 5] [--rounds 5] [--read] [--out F]
+`--lib NAME` measures tools/variants/NAME/libingot_gpu.so (another build, e.g.
+the parent commit from tools/build_tree_variant.sh) instead of the in-tree one.
+
+    python tools/csum_probe.py [--frames N] [--reps 5] [--rounds 5] [--read] [--lib NAME]
+        [--out F]
 """
 from __future__ import annotations
 
@@ -53,7 +57,12 @@ def main():
     ap.add_argument("--read", action="store_true",
                     help="add the chunked calls (checksum_verify_read / _fill_read) on c3")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--lib", default=None, help="tools/variants/<name>/libingot_gpu.so instead")
     args = ap.parse_args()
+    if args.lib:
+        from ingot_amd import _lib as L
+
+        L.LIB_PATH = ROOT / "tools" / "variants" / args.lib / "libingot_gpu.so"
 
     import torch
 
@@ -174,7 +183,8 @@ def main():
             e1.record(s)
             torch.cuda.synchronize()
             res[k].append(e0.elapsed_time(e1) * 1e3 / args.reps)
-    out = {"what": __doc__.split("\n\n")[0], "layouts": meta, "reps": args.reps, "runs": {}}
+    out = {"what": __doc__.split("\n\n")[0], "lib": args.lib or "in-tree", "layouts": meta,
+           "reps": args.reps, "runs": {}}
     for k, v in res.items():
         us = statistics.median(v)
         out["runs"][k] = {"us": round(us, 1), "rounds": [round(x, 1) for x in v],

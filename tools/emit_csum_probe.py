@@ -38,7 +38,7 @@ an empty chunk where the record is not Ok), rows
 checks once that c and d, and e and f, leave identical bytes, and compares the
 rounds' ranges: the new row's maximum against the old row's minimum.
 
-`--usage-only` compiles ingot_amd/csrc/emit.hip with
+`--usage-only` compiles ingot_amd/csrc/emit.hip, emit_read.hip and csum.hip with
 -Rpass-analysis=kernel-resource-usage and writes the kernels' figures (no GPU
 needed); `--usage FILE` attaches such a file to the result.
 
@@ -60,10 +60,10 @@ sys.path.insert(0, str(ROOT))
 
 
 def resource_usage() -> dict:
-    """k_emit's and k_emit_read's instantiations -> registers, scratch,
-    occupancy (from hipcc)."""
+    """k_emit's and k_emit_read's instantiations and the two checksum kernels
+    -> registers, scratch, occupancy, static LDS (from hipcc)."""
     err = ""
-    for src in ("emit.hip", "emit_read.hip"):
+    for src in ("emit.hip", "emit_read.hip", "csum.hip"):
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
                f"-I{ROOT / 'include'}", "-Rpass-analysis=kernel-resource-usage", "-c",
                str(ROOT / "ingot_amd" / "csrc" / src), "-o", "/dev/null"]
@@ -71,7 +71,7 @@ def resource_usage() -> dict:
     out, cur = {}, None
     names = {"k_emitILb1ELb1EE": "k_emit<copy, sums>", "k_emitILb1ELb0EE": "k_emit<copy>",
              "k_emitILb0ELb0EE": "k_emit<headers>", "k_emit_readILb1EE": "k_emit_read<sums>",
-             "k_emit_readILb0EE": "k_emit_read"}
+             "k_emit_readILb0EE": "k_emit_read", "6k_csumE": "k_csum", "11k_csum_readE": "k_csum_read"}
     for line in err.splitlines():
         m = re.search(r"remark: +([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+)", line)
         if not m:
@@ -81,7 +81,7 @@ def resource_usage() -> dict:
             cur = next((v for k, v in names.items() if k in val), val)
             out[cur] = {}
         elif cur and key in ("TotalSGPRs", "VGPRs", "AGPRs", "ScratchSize", "Occupancy",
-                             "SGPRs Spill", "VGPRs Spill"):
+                             "SGPRs Spill", "VGPRs Spill", "LDS Size"):
             out[cur][key] = int(val)
     return out
 
