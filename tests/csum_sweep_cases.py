@@ -196,6 +196,18 @@ def batch(chain, layout: str, prepared: bool = False) -> Batch:
     return b
 
 
+def source_frames(chain, layout: str = "indexed"):
+    """The frames batch(chain, layout) is made of."""
+    return _source_frames(chain, layout)
+
+
+def batch_of(frames, chain, prepare=None) -> Batch:
+    """An indexed batch of `frames` as batch(chain, "indexed") lays them out,
+    every sum made valid; prepare(arena, off, lens, chain) runs before the
+    fill."""
+    return _indexed_from(list(frames), chain, prepare)
+
+
 @lru_cache(maxsize=None)
 def batch_at(chain, mis: int) -> Batch:
     """The chain's frames (once), every one of them `mis` bytes into a 16-B

@@ -102,9 +102,51 @@ def sums(b, a, chain, rec, what: int, o_udp=None) -> None:
         upd._apply(a, o + 6, upd.delta(b, a, [(o, L), (14 + 8, 14 + 40)], o + 6), True)
 
 
+def apply_whats(arena, off, lens, chain, edits, whats, rows=None, n_rows: int = 0,
+                stride: int = 0, n=None):
+    """apply() for several `what` values at once -> ([the arena after the call
+    under each of `whats`], the records).  The edits do not depend on `what`,
+    so they are made once; a frame whose bytes they left as they were has D = 0
+    for every sum (no field is written) and is not summed."""
+    for what in whats:
+        if what & ~(CSUM_L3 | CSUM_L4 | CSUM_OUTER_L4) or ((what & CSUM_OUTER_L4) and chain != TUN):
+            raise ValueError("what")
+    if n is None:
+        n = len(off)
+    recs = oracle.parse_batch(arena, off, lens, chain, stride=stride, n=n)
+    outer = None
+    if chain == TUN:
+        outer = oracle.geneve_fields_batch(arena, off, lens, stride=stride, n=n)["outer"]
+    plain = np.array(arena)
+    moved = []
+    for i in range(n):
+        if int(recs["status"][i]) != 0:
+            continue
+        if rows is not None and int(rows[i]) >= n_rows:
+            continue
+        o = int(off[i]) if off is not None else i * stride
+        ln = int(lens[i]) if lens is not None else stride
+        if off is None:
+            ln = min(ln, stride)  # a slot holds at most one frame
+        out_i = outer[i] if chain == TUN else None
+        edit_packet(plain[o:o + ln], chain, recs[i], out_i, edits, i, rows)
+        if plain[o:o + ln].tobytes() != arena[o:o + ln].tobytes():
+            moved.append((i, o, ln))
+    out = []
+    for what in whats:
+        want = plain.copy()
+        for i, o, ln in moved if what else ():
+            sums(arena[o:o + ln], want[o:o + ln], chain, recs[i], what,
+                 int(outer[i]["outer_udp_off"]) if chain == TUN else None)
+        out.append(want)
+    return out, recs
+
+
 def apply(arena, off, lens, chain, edits, rows=None, n_rows: int = 0, what: int = 0,
           stride: int = 0, n=None):
-    """-> (the arena after the call, the records)."""
+    """-> (the arena after the call, the records).  Every frame that is edited
+    is summed, changed or not (apply_whats' shortcut is held to this by
+    tests/test_modify_rows_sweep_model.py)."""
     if what & ~(CSUM_L3 | CSUM_L4 | CSUM_OUTER_L4) or ((what & CSUM_OUTER_L4) and chain != TUN):
         raise ValueError("what")
     if n is None:
