@@ -839,7 +839,8 @@ enum ingot_emit_source {
     INGOT_EMIT_LENGTH = 0,
     INGOT_EMIT_U16 = 1,
     INGOT_EMIT_U32 = 2,
-    INGOT_EMIT_VALUE = 3
+    INGOT_EMIT_VALUE = 3,
+    INGOT_EMIT_BYTES = 4   /* only valid in ingot_emit_set_rows (ingot_gpu_emit_packets_rows) */
 };
 #define INGOT_MAX_EMIT_SETS 8
 #define INGOT_MAX_EMIT_HDR 256
@@ -1279,7 +1280,8 @@ int ingot_gpu_parse_modify_csum(ingot_gpu_ctx* ctx, uint8_t* d_arena,
  * Out of scope: the slot-ring kernel (slots >= 64 B without a length array
  * run the plain per-tile kernel here, whatever INGOT_TUNE_PIPELINE says); the
  * chunked form (ingot_gpu_parse_read_modify takes no tables); ops other than
- * SET on wide fields; wide fields in ingot_edit and in the emit calls.
+ * SET on wide fields; wide fields in ingot_edit (the emit takes them in
+ * ingot_gpu_emit_packets_rows, below).
  * ------------------------------------------------------------------------- */
 enum ingot_wide_field {            /* only valid in ingot_edit_rows.field */
     INGOT_FW_ETH_DESTINATION = 64, /* ethernet.rs, 6 B at +0  */
@@ -1316,6 +1318,107 @@ int ingot_gpu_parse_modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena,
                                 const ingot_edit_rows* edits, uint32_t n_edits,
                                 const uint32_t* d_row, uint32_t n_rows,
                                 uint32_t what, ingot_rec* d_out, void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Emit with per-packet and per-row header operands: ingot_gpu_emit_packets_csum
+ * whose setters take the operand forms of ingot_gpu_parse_modify_rows, the
+ * Ethernet and IPv6 addresses included.  One launch encapsulates every packet
+ * towards its own flow's endpoint (OPTE's outbound Geneve-over-IPv6: the outer
+ * IPv6 destination, the next-hop MAC and the VNI of the mapping the flow
+ * resolved to) and fills the outer sums over those per-packet bytes.
+ * Build-defined; tests/emit_rows_model.py is the definition.
+ *
+ * Frames, header block, sums.  The frames, the header block `hdr`, the LENGTH
+ * and VALUE sources, the sums (n_sums == 0: none), the source reads, the
+ * destination writes, the alignment rules and the LDS-fit ERANGE are exactly
+ * ingot_gpu_emit_packets_csum's.  `sets` is host memory
+ * (<= INGOT_MAX_EMIT_SETS; a wide field counts as one).
+ *
+ * Fields.  `field` is an ingot_field, or one of ingot_wide_field: for the
+ * header at `at`, the Ethernet destination / source (6 B at at + 0 / at + 6)
+ * or the IPv6 source / destination (16 B at at + 8 / at + 24).  As for narrow
+ * fields nothing is derived: the caller names `at`, and the field must lie
+ * inside hdr.  Wide fields take only INGOT_EMIT_BYTES, and BYTES is valid only
+ * for them.
+ *
+ * Operand of set k for packet i, by `source`:
+ *   INGOT_EMIT_LENGTH / _VALUE  as in ingot_emit_set;
+ *   otherwise the row index is r = i (INGOT_BY_PACKET) or d_row[i]
+ *   (INGOT_BY_ROW) and the row is (const uint8_t*)d_values + r * pitch
+ *   (pitch 0: the source's width, i.e. a dense array; the product is taken in
+ *   64 bits);
+ *   INGOT_EMIT_U16 / _U32  the host-endian integer at the row, + add, modulo
+ *       2^width;
+ *   INGOT_EMIT_BYTES  the field's 6 or 16 bytes in wire order at the row, at
+ *       any address.
+ * Several sets may point into one table at different offsets (d_values = the
+ * table + the member's offset, pitch = the row size).
+ *
+ * Order.  The setters apply in list order to the packet's copy of the block: a
+ * later set overwrites what an earlier one wrote, and a wide and a narrow set
+ * may overlap.  The sums are taken after all setters, so the UDP pseudo-header
+ * sees the per-packet addresses.
+ *
+ * Row guard.  With d_row given, a packet whose d_row[i] >= n_rows is not
+ * emitted: no byte is stored at or around d_dst + d_dst_off[i], no source byte
+ * and no table is read for it (INGOT_ROW_NONE is the largest such value, so the
+ * d_flow array of ingot_gpu_flow_hist can be passed as d_row with a table of
+ * `bins` rows).  This is the emit's form of the rewrite's "not touched at
+ * all": a flow without a mapping goes to the slow path, it is not
+ * encapsulated towards a made-up endpoint.  With d_row NULL no set may be
+ * BY_ROW (EINVAL) and n_rows is ignored.  Table reads are bounded by the row
+ * guard alone: a BY_PACKET table holds n rows, a BY_ROW table n_rows.
+ *
+ * Equivalence.  For every emitted packet the bytes are those
+ * ingot_gpu_emit_packets_csum writes for that packet alone when each table set
+ * is replaced by a VALUE set of the row's value and each BYTES set's row is
+ * pasted into hdr at its place in list order.  With no BYTES set, no BY_ROW
+ * set and d_row NULL, the output is byte-identical to
+ * ingot_gpu_emit_packets_csum with the same sets and sums.
+ *
+ * EINVAL, all checked before any device work, in this order:
+ *   1. ctx NULL;
+ *   2. ingot_gpu_emit_packets's checks of hdr / hdr_len / n_sets / NULL sets;
+ *   3. per set, in list order: a field that is neither an ingot_field nor a
+ *      wide field; source > INGOT_EMIT_BYTES; non-zero `_pad`; by >
+ *      INGOT_BY_ROW; BYTES on a narrow field, or another source on a wide
+ *      field; LENGTH / VALUE with `by`, `pitch` or `d_values` non-zero; a table
+ *      source with NULL d_values; BYTES with add != 0; `pitch` non-zero and
+ *      below the source's width; U16 / U32 with d_values or pitch not a
+ *      multiple of 2 / 4; BY_ROW without d_row; a field not inside hdr;
+ *   4. ingot_gpu_emit_packets_csum's checks of `sums`, unchanged (the version /
+ *      ihl setter rule applies to the narrow sets);
+ *   5. n == 0 succeeds;
+ *   6. any of d_src, d_off, d_len, d_dst, d_dst_off NULL;
+ *   7. then ERANGE from the LDS-fit check.
+ *
+ * Out of scope: the header-block-only form (ingot_gpu_emit_headers) and the
+ * chunked form (ingot_gpu_emit_packets_read) take no tables; wide fields in
+ * ingot_emit_set and ingot_edit; a per-packet "emitted" flag (the caller has
+ * d_row).
+ * ------------------------------------------------------------------------- */
+typedef struct ingot_emit_set_rows {
+    uint16_t at;           /* as ingot_emit_set */
+    uint8_t  field;        /* enum ingot_field or enum ingot_wide_field */
+    uint8_t  source;       /* enum ingot_emit_source, incl. INGOT_EMIT_BYTES */
+    int32_t  add;          /* as ingot_emit_set; must be 0 for BYTES */
+    uint8_t  by;           /* enum ingot_edit_by; must be 0 for LENGTH / VALUE */
+    uint8_t  _pad[3];      /* must be 0 */
+    uint32_t pitch;        /* bytes between rows; 0 = the source's width */
+    const void* d_values;  /* device memory; must be NULL for LENGTH / VALUE */
+} ingot_emit_set_rows;
+
+#ifdef __cplusplus
+static_assert(sizeof(ingot_emit_set_rows) == 24, "ingot_emit_set_rows is 24 bytes");
+#endif
+
+int ingot_gpu_emit_packets_rows(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
+                                const ingot_emit_set_rows* sets, uint32_t n_sets,
+                                const ingot_emit_sum* sums, uint32_t n_sums,
+                                const uint32_t* d_row, uint32_t n_rows,
+                                const uint8_t* d_src, const uint64_t* d_off,
+                                const uint16_t* d_len, uint64_t n, uint8_t* d_dst,
+                                const uint64_t* d_dst_off, void* stream);
 
 /* ---------------------------------------------------------------------------
  * The rewrite over chunked packets: ingot_gpu_parse_read, then ingot's setters

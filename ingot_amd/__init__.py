@@ -70,6 +70,7 @@ from .abi import (  # noqa: F401  (re-exports)
     WideField,
     edit_rows_array,
     edits_array,
+    emit_set_rows_array,
     emit_sets_array,
     emit_sums_array,
     rec16_to_rec8,
@@ -516,12 +517,40 @@ class Context:
             "ingot_gpu_parse_modify")
         return out
 
+    def _row_table(self, name: str, t, field, by_row: bool, n: int, n_rows: int):
+        """One operand table of parse_modify_rows / emit_packets_rows, validated
+        on the host -> ("U16" | "U32" | "BYTES", pitch): dtype, unit stride in
+        its last dimension, a row stride that holds the source's width, and
+        enough rows for the packets (by packet) or for n_rows (by row)."""
+        dt = str(t.dtype).replace("torch.", "")
+        if int(field) in WIDE_BYTES:
+            width = WIDE_BYTES[WideField(int(field))]
+            if dt != "uint8" or t.dim() != 2 or t.shape[1] != width:
+                raise ValueError(f"{name} must be uint8 of shape (rows, {width}), not {dt} "
+                                 f"{tuple(t.shape)}")
+            source = "BYTES"
+        else:
+            if dt not in _U16 + _U32:
+                raise ValueError(f"{name} must be {' or '.join(_U16 + _U32)}, not {dt}")
+            if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] != 1):
+                raise ValueError(f"{name} must have shape (rows,) or (rows, 1)")
+            source = "U16" if dt in _U16 else "U32"
+            width = 2 if dt in _U16 else 4
+        if t.shape[-1] > 1 and t.stride(-1) != 1:
+            raise ValueError(f"{name} must be contiguous in its last dimension")
+        pitch = t.stride(0) * t.element_size() if t.shape[0] > 1 else width
+        if pitch < width:
+            raise ValueError(f"{name}: rows {pitch} B apart cannot hold {width} B")
+        need = n_rows if by_row else n
+        if t.shape[0] < need:
+            raise ValueError(f"{name} holds {t.shape[0]} rows, needs at least {need}")
+        self._on_device(**{name: t})
+        return source, pitch
+
     def _edit_rows(self, edits, n: int, rows, n_rows: int):
         """parse_modify_rows' edit list -> (ingot_edit_rows array, tensors kept
-        alive for the call).  Every table is validated here, on the host:
-        dtype, unit stride in its last dimension, a row stride that holds the
-        source's width, and enough rows for the packets (by packet) or for
-        n_rows (by row)."""
+        alive for the call).  Every table is validated here, on the host
+        (_row_table)."""
         out, keep = [], []
         for k, e in enumerate(edits):
             layer, field, op, operand = e[0], e[1], e[2], e[3]
@@ -540,32 +569,11 @@ class Context:
                 out.append((layer, field, op, index, int(operand) & 0xFFFFFFFF, EditSource.VALUE,
                             EditBy.PACKET, 0, 0))
                 continue
-            t, name = operand, f"edit {k}'s table"
-            dt = str(t.dtype).replace("torch.", "")
-            if wide:
-                width = WIDE_BYTES[WideField(int(field))]
-                if dt != "uint8" or t.dim() != 2 or t.shape[1] != width:
-                    raise ValueError(f"{name} must be uint8 of shape (rows, {width}), not {dt} "
-                                     f"{tuple(t.shape)}")
-                source = EditSource.BYTES
-            else:
-                if dt not in _U16 + _U32:
-                    raise ValueError(f"{name} must be {' or '.join(_U16 + _U32)}, not {dt}")
-                if t.dim() not in (1, 2) or (t.dim() == 2 and t.shape[1] != 1):
-                    raise ValueError(f"{name} must have shape (rows,) or (rows, 1)")
-                source = EditSource.U16 if dt in _U16 else EditSource.U32
-                width = 2 if dt in _U16 else 4
-            if t.shape[-1] > 1 and t.stride(-1) != 1:
-                raise ValueError(f"{name} must be contiguous in its last dimension")
-            pitch = t.stride(0) * t.element_size() if t.shape[0] > 1 else width
-            if pitch < width:
-                raise ValueError(f"{name}: rows {pitch} B apart cannot hold {width} B")
-            need = n_rows if by == EditBy.ROW else n
-            if t.shape[0] < need:
-                raise ValueError(f"{name} holds {t.shape[0]} rows, needs at least {need}")
-            self._on_device(**{name: t})
+            t = operand
+            source, pitch = self._row_table(f"edit {k}'s table", t, field, by == EditBy.ROW, n,
+                                            n_rows)
             keep.append(t)
-            out.append((layer, field, op, index, 0, source, by, pitch, t.data_ptr()))
+            out.append((layer, field, op, index, 0, EditSource[source], by, pitch, t.data_ptr()))
         return edit_rows_array(out), keep
 
     def parse_modify_rows(self, arena, off, lens, chain: Chain, edits, rows=None,
@@ -679,6 +687,67 @@ class Context:
             self._h, ctypes.addressof(h), len(hdr), s.ctypes.data_as(ctypes.c_void_p), len(s),
             _ptr(src), _ptr(off), _ptr(lens), n, _ptr(dst), _ptr(dst_off),
             _stream(stream, self.device)), "ingot_gpu_emit_packets")
+        return dst
+
+    def emit_packets_rows(self, hdr: bytes, sets, src, off, lens, dst, dst_off, rows=None,
+                          n_rows: int = 0, sums=None, stream=None):
+        """emit_packets whose setters take per-packet and per-row operands, the
+        Ethernet and IPv6 addresses included (ingot_gpu_emit_packets_rows):
+        sets = [(at, Field | WideField, EmitSource, add[, table]), ...].
+        `table` is a cuda tensor with one row per packet, or ("row", tensor)
+        to take row rows[i] instead of row i: uint16 / int16 (U16) or uint32 /
+        int32 (U32) of shape (rows,) or (rows, 1), or, for a WideField
+        (EmitSource.BYTES), uint8 of shape (rows, 6 | 16) holding the bytes in
+        wire order.  A tensor's row stride is the table's pitch, so columns of
+        one (rows, 32) uint8 endpoint table can be passed as views.
+
+        `rows` holds n uint32 values; a packet whose rows[i] >= n_rows
+        (ROW_NONE, flow_hist's bin of an uncounted packet) is not emitted: no
+        byte of dst is written for it.  sums as in emit_packets (None: none),
+        taken after all setters.  Returns dst."""
+        n = off.numel()
+        hdr = bytes(hdr)
+        self._arg("src", src, _U8)
+        self._arg("off", off, _U64, n)
+        self._arg("lens", lens, _U16, n)
+        self._arg("dst", dst, _U8)
+        self._arg("dst_off", dst_off, _U64, n)
+        self._arg("rows", rows, _U32, n, optional=True)
+        if rows is not None and (n_rows < 0 or n_rows > 0xFFFFFFFF):
+            raise ValueError("n_rows must fit 32 bits")
+        self._on_device(src=src, off=off, lens=lens, dst=dst, dst_off=dst_off, rows=rows)
+        out, keep = [], []
+        for k, e in enumerate(sets):
+            at, field, source, add = e[0], e[1], EmitSource(int(e[2])), e[3]
+            table, by = (e[4] if len(e) > 4 else None), EditBy.PACKET
+            if isinstance(table, tuple):
+                if len(table) != 2 or table[0] != "row":
+                    raise ValueError(f"set {k}: a table operand is a tensor or ('row', tensor)")
+                if rows is None:
+                    raise ValueError(f"set {k}: ('row', tensor) needs `rows`")
+                by, table = EditBy.ROW, table[1]
+            if source in (EmitSource.LENGTH, EmitSource.VALUE):
+                if table is not None:
+                    raise ValueError(f"set {k}: {source.name} takes no table")
+                out.append((at, field, source, add, 0, 0, 0))
+                continue
+            if not hasattr(table, "data_ptr"):
+                raise ValueError(f"set {k}: {source.name} needs a cuda tensor")
+            kind, pitch = self._row_table(f"set {k}'s table", table, field, by == EditBy.ROW, n,
+                                          int(n_rows))
+            if kind != source.name:
+                raise ValueError(f"set {k}: a {kind} table for an EmitSource.{source.name} set")
+            keep.append(table)
+            out.append((at, field, source, add, by, pitch, table.data_ptr()))
+        s = emit_set_rows_array(out)
+        cs = emit_sums_array(sums or ())
+        h = (ctypes.c_uint8 * max(len(hdr), 1)).from_buffer_copy(hdr or b"\0")
+        _lib.check(self._lib.ingot_gpu_emit_packets_rows(
+            self._h, ctypes.addressof(h), len(hdr), s.ctypes.data_as(ctypes.c_void_p), len(s),
+            cs.ctypes.data_as(ctypes.c_void_p), len(cs), _ptr(rows), int(n_rows), _ptr(src),
+            _ptr(off), _ptr(lens), n, _ptr(dst), _ptr(dst_off), _stream(stream, self.device)),
+            "ingot_gpu_emit_packets_rows")
+        del keep
         return dst
 
     def emit_packets_read(self, hdr: bytes, sets, src, seg_off, seg_len, pkt_seg, dst, dst_off,

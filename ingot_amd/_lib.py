@@ -136,6 +136,11 @@ SIGNATURES = {
         [ctypes.c_void_p, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint32,
          c_u8p, c_u8p, c_u8p, c_u64, c_u8p, c_u8p, ctypes.c_void_p],
     ),
+    "ingot_gpu_emit_packets_rows": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint32,
+         c_u8p, ctypes.c_uint32, c_u8p, c_u8p, c_u8p, c_u64, c_u8p, c_u8p, ctypes.c_void_p],
+    ),
     "ingot_gpu_emit_packets_read": (
         ctypes.c_int,
         [ctypes.c_void_p, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint32,

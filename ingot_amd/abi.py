@@ -417,6 +417,7 @@ class EmitSource(enum.IntEnum):
     U16 = 1     # a u16 per packet (device array) + add
     U32 = 2     # a u32 per packet (device array) + add
     VALUE = 3   # `add` for every packet
+    BYTES = 4   # ingot_emit_set_rows only: a wide field's 6 or 16 bytes in wire order per row
 
 
 MAX_EMIT_SETS = 8
@@ -440,6 +441,29 @@ def emit_sets_array(sets) -> np.ndarray:
         add = ((int(e[3]) + (1 << 31)) % (1 << 32)) - (1 << 31)  # modulo 2^32, as the C int32
         a[k]["at"], a[k]["field"], a[k]["source"], a[k]["add"] = e[0], int(e[1]), int(e[2]), add
         a[k]["d_values"] = e[4] if len(e) > 4 and e[4] is not None else 0
+    return a
+
+
+class IngotEmitSetRows(ctypes.Structure):
+    _fields_ = [("at", U16), ("field", U8), ("source", U8), ("add", ctypes.c_int32), ("by", U8),
+                ("_pad", U8 * 3), ("pitch", U32), ("d_values", ctypes.c_void_p)]
+
+
+assert ctypes.sizeof(IngotEmitSetRows) == 24
+EMIT_SET_ROWS_DTYPE = np.dtype([("at", "<u2"), ("field", "u1"), ("source", "u1"), ("add", "<i4"),
+                                ("by", "u1"), ("_pad", "u1", (3,)), ("pitch", "<u4"),
+                                ("d_values", "<u8")])
+assert EMIT_SET_ROWS_DTYPE.itemsize == 24
+
+
+def emit_set_rows_array(sets) -> np.ndarray:
+    """[(at, field, EmitSource, add, by, pitch, values pointer), ...] ->
+    ingot_emit_set_rows array (ingot_gpu_emit_packets_rows)."""
+    a = np.zeros(len(sets), dtype=EMIT_SET_ROWS_DTYPE)
+    for k, e in enumerate(sets):
+        add = ((int(e[3]) + (1 << 31)) % (1 << 32)) - (1 << 31)  # modulo 2^32, as the C int32
+        a[k]["at"], a[k]["field"], a[k]["source"], a[k]["add"] = e[0], int(e[1]), int(e[2]), add
+        a[k]["by"], a[k]["pitch"], a[k]["d_values"] = int(e[4]), int(e[5]), int(e[6] or 0)
     return a
 
 

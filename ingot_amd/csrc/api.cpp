@@ -985,9 +985,111 @@ int emit_packets(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
     return from_hip(ingot_gpu::launch_emit(a, (hipStream_t)stream));
 }
 
+// ingot_gpu_emit_packets_rows: the set list -> the pieces of EmitRowsArgs, every
+// check in the order the header gives.  `narrow` receives the (at, field) of
+// the narrow sets, for emit_sums' version / ihl rule.
+int emit_rows_pieces(const ingot_emit_set_rows* sets, uint32_t n_sets, bool have_row,
+                     uint32_t hdr_len, ingot_gpu::EmitRowsArgs& a, ingot_emit_set* narrow,
+                     uint32_t& n_narrow) {
+    using namespace ingot_gpu;
+    uint32_t np = 0;
+    n_narrow = 0;
+    for (uint32_t k = 0; k < n_sets; ++k) {
+        const ingot_emit_set_rows& e = sets[k];
+        const bool wide = e.field >= INGOT_FW_ETH_DESTINATION && e.field <= INGOT_FW_V6_DESTINATION;
+        if (!wide && e.field >= INGOT_F_COUNT) return INGOT_GPU_EINVAL;
+        if (e.source > INGOT_EMIT_BYTES) return INGOT_GPU_EINVAL;
+        if (e._pad[0] || e._pad[1] || e._pad[2]) return INGOT_GPU_EINVAL;
+        if (e.by > INGOT_BY_ROW) return INGOT_GPU_EINVAL;
+        if ((e.source == INGOT_EMIT_BYTES) != wide) return INGOT_GPU_EINVAL;
+        const bool table = e.source != INGOT_EMIT_LENGTH && e.source != INGOT_EMIT_VALUE;
+        if (!table && (e.by || e.pitch || e.d_values)) return INGOT_GPU_EINVAL;
+        if (table && !e.d_values) return INGOT_GPU_EINVAL;
+        if (wide && e.add != 0) return INGOT_GPU_EINVAL;
+        const bool mac = e.field == INGOT_FW_ETH_DESTINATION || e.field == INGOT_FW_ETH_SOURCE;
+        const uint32_t width = e.source == INGOT_EMIT_U16   ? 2u
+                               : e.source == INGOT_EMIT_U32 ? 4u
+                               : wide                       ? (mac ? 6u : 16u)
+                                                            : 0u;
+        if (e.pitch && e.pitch < width) return INGOT_GPU_EINVAL;
+        if ((e.source == INGOT_EMIT_U16 || e.source == INGOT_EMIT_U32) &&
+            (((uintptr_t)e.d_values | e.pitch) & (width - 1u)))
+            return INGOT_GPU_EINVAL;
+        if (e.by == INGOT_BY_ROW && !have_row) return INGOT_GPU_EINVAL;
+        const uint32_t pitch = e.pitch ? e.pitch : width;
+        const uint8_t* values = static_cast<const uint8_t*>(e.d_values);
+        if (!wide) {
+            const FieldGeo g = kFieldGeo[e.field];
+            const uint32_t pos = (uint32_t)e.at + g.bit / 8u;  // 32 bits: no wrap before the check
+            const uint32_t nbytes = (g.bit % 8u + g.bits + 7u) / 8u;
+            if (pos + nbytes > hdr_len) return INGOT_GPU_EINVAL;  // field inside hdr
+            a.p[np++] = EmitPiece{(uint16_t)pos, e.at, (uint8_t)nbytes,
+                                  (uint8_t)((8u - ((g.bit + g.bits) % 8u)) % 8u), g.bits,
+                                  e.source,  // LENGTH / U16 / U32 / VALUE are EmitPieceSource's first
+                                  e.by, {0, 0, 0}, e.add, pitch, values};
+            narrow[n_narrow++] = ingot_emit_set{e.at, e.field, e.source, e.add, nullptr};
+            continue;
+        }
+        // a wide field: big-endian pieces of 4 (and, a MAC's last, 2) bytes
+        const uint32_t pos = (uint32_t)e.at + (mac ? (e.field == INGOT_FW_ETH_SOURCE ? 6u : 0u)
+                                                   : (e.field == INGOT_FW_V6_DESTINATION ? 24u : 8u));
+        if (pos + width > hdr_len) return INGOT_GPU_EINVAL;  // field inside hdr
+        for (uint32_t b = 0; b < width; b += 4u) {
+            const uint32_t nb = width - b < 4u ? width - b : 4u;
+            const bool aligned = !(((uintptr_t)(values + b) | pitch) & (nb - 1u));
+            a.p[np++] = EmitPiece{(uint16_t)(pos + b), 0, (uint8_t)nb, 0, (uint8_t)(8u * nb),
+                                  (uint8_t)(nb == 4u ? (aligned ? EP_BE32A : EP_BE32)
+                                                     : (aligned ? EP_BE16A : EP_BE16)),
+                                  e.by, {0, 0, 0}, 0, pitch, values + b};
+        }
+    }
+    a.n_pieces = np;
+    return INGOT_GPU_SUCCESS;
+}
+
+int emit_packets_rows(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
+                      const ingot_emit_set_rows* sets, uint32_t n_sets,
+                      const ingot_emit_sum* sums, uint32_t n_sums, const uint32_t* d_row,
+                      uint32_t n_rows, const uint8_t* d_src, const uint64_t* d_off,
+                      const uint16_t* d_len, uint64_t n, uint8_t* d_dst,
+                      const uint64_t* d_dst_off, void* stream) {
+    if (!ctx) return INGOT_GPU_EINVAL;
+    ingot_gpu::EmitRowsArgs a{};
+    if (n_sets > INGOT_MAX_EMIT_SETS || (n_sets && !sets)) return INGOT_GPU_EINVAL;
+    if (int e = emit_args(hdr, hdr_len, nullptr, 0, a.e)) return e;
+    ingot_emit_set narrow[INGOT_MAX_EMIT_SETS];
+    uint32_t n_narrow = 0;
+    if (int e = emit_rows_pieces(sets, n_sets, d_row != nullptr, hdr_len, a, narrow, n_narrow))
+        return e;
+    if (int e = emit_sums(hdr, hdr_len, narrow, n_narrow, sums, n_sums, a.e)) return e;
+    if (n == 0) return INGOT_GPU_SUCCESS;
+    if (!d_src || !d_off || !d_len || !d_dst || !d_dst_off) return INGOT_GPU_EINVAL;
+    if (ingot_gpu::emit_rows_lds_bytes(a) > ctx->lds_bytes) return INGOT_GPU_ERANGE;
+    if (int e = enter(ctx)) return e;
+    a.e.src = d_src;
+    a.e.off = d_off;
+    a.e.len = d_len;
+    a.e.dst = d_dst;
+    a.e.dst_off = d_dst_off;
+    a.e.n = n;
+    a.row = d_row;
+    a.n_rows = n_rows;
+    return from_hip(ingot_gpu::launch_emit_rows(a, (hipStream_t)stream));
+}
+
 }  // namespace
 
 extern "C" {
+
+int ingot_gpu_emit_packets_rows(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
+                                const ingot_emit_set_rows* sets, uint32_t n_sets,
+                                const ingot_emit_sum* sums, uint32_t n_sums,
+                                const uint32_t* d_row, uint32_t n_rows, const uint8_t* d_src,
+                                const uint64_t* d_off, const uint16_t* d_len, uint64_t n,
+                                uint8_t* d_dst, const uint64_t* d_dst_off, void* stream) {
+    return emit_packets_rows(ctx, hdr, hdr_len, sets, n_sets, sums, n_sums, d_row, n_rows, d_src,
+                             d_off, d_len, n, d_dst, d_dst_off, stream);
+}
 
 int ingot_gpu_emit_packets(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
                            const ingot_emit_set* sets, uint32_t n_sets, const uint8_t* d_src,

@@ -1,5 +1,6 @@
 // emit.hip — batched Emit (ingot_gpu_emit_packets / ingot_gpu_emit_headers /
-// ingot_gpu_emit_packets_csum: the SUMS instantiation, described where it starts).
+// ingot_gpu_emit_packets_csum: the SUMS instantiation, described where it starts /
+// ingot_gpu_emit_packets_rows: the ROWS instantiations, described at k_emit).
 //
 // ingot's Emit (ingot-types/src/emit.rs:8-120) writes an owned header stack
 // field by field (the generated emit_raw, ingot-macros/src/packet/mod.rs:
@@ -25,6 +26,8 @@
 // packet shares with its neighbours as predicated pieces (store_edge).
 // HBM-bound copy: algorithmic bytes per packet = len + 24 B of descriptors
 // and set values read, hdr_len + len written.
+#include <type_traits>
+
 #include "emit_common.h"
 
 namespace ingot_gpu {
@@ -59,6 +62,8 @@ template <bool COPY> struct Shape {
 #define INGOT_EMIT_UNROLL 4
 #endif
 constexpr uint32_t UNROLL = INGOT_EMIT_UNROLL;  // 64-chunk steps whose loads fly together
+// WaveDesc::mis of a packet the row guard holds back (no packet's dmis | s_mis << 8)
+constexpr uint32_t GUARDED = 0xffffffffu;
 
 // Per-wave LDS: the 64 packets' descriptors, the inclusive prefix of their
 // chunk counts, and each packet's patched header block at its destination's
@@ -75,9 +80,21 @@ struct WaveDesc {
     uint32_t _pad[WAVE - 6];
 };
 
-template <bool COPY, bool SUMS = false>
-__global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
+// The EmitArgs of either argument block.
+__device__ __forceinline__ const EmitArgs& emit_args_of(const EmitArgs& a) { return a; }
+__device__ __forceinline__ const EmitArgs& emit_args_of(const EmitRowsArgs& a) { return a.e; }
+
+// ROWS (ingot_gpu_emit_packets_rows, whole packets only; its argument block is
+// EmitRowsArgs): the prologue also loads the packet's row index, folds the row
+// guard into `live` and takes the setters' operands from the pieces of
+// EmitRowsArgs; a guarded packet has no chunks, so the walk never meets it,
+// and step 5 skips it.  Everything after the prologue is the same code.
+template <bool COPY, bool SUMS = false, bool ROWS = false>
+__global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(
+    std::conditional_t<ROWS, EmitRowsArgs, EmitArgs> args) {
     static_assert(COPY || !SUMS, "sums need the payload: whole packets only");
+    static_assert(COPY || !ROWS, "rows: whole packets only");
+    const EmitArgs& a = emit_args_of(args);
     constexpr uint32_t BLOCK = Shape<COPY>::BLOCK, W = Shape<COPY>::W, G = Shape<COPY>::G;
     constexpr uint32_t PW = Shape<COPY>::PW, NP = Shape<COPY>::NP;
     constexpr uint32_t NPOW = NP <= 64 ? 64 : NP <= 128 ? 128 : 256;  // search span
@@ -94,6 +111,9 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
     // SUMS (G == 1): after the regions, the parked chunks, then the accumulators
     u32x4* park = reinterpret_cast<u32x4*>(smem + TB * 16 + G * sizeof(Desc) + G * NP * RS);
     uint32_t* acc = reinterpret_cast<uint32_t*>(park + 2u * NP);
+    // ROWS: the pieces, after everything else
+    EmitPiece* pieces = reinterpret_cast<EmitPiece*>(SUMS ? (void*)(acc + NP) : (void*)park);
+    if constexpr (ROWS) load_pieces(pieces, args, BLOCK);
     const bool udp = SUMS && a.sums.udp;
     const uint32_t fpos = (uint32_t)a.sums.udp_at + 6u;  // the UDP checksum field in hdr
     __syncthreads();
@@ -103,10 +123,22 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
         //    descriptor and set-value loads)
         const uint32_t j = wg * WAVE + lane;  // the packet's index in the group
         const uint64_t i = base + j;
-        const bool live = i < a.n;
-        const uint32_t L = live ? (uint32_t)gbl(a.len)[i] : 0u;
-        const uint64_t doff = live ? (a.dst_off ? gbl(a.dst_off)[i] : i * (uint64_t)a.stride) : 0u;
-        const uint64_t soff = (COPY && live) ? gbl(a.off)[i] : 0u;
+        bool live = i < a.n;
+        uint32_t r = 0;  // ROWS: the packet's row index, loaded with its descriptors
+        if constexpr (ROWS) {
+            if (live && args.row) r = gbl(args.row)[i];
+        }
+        uint32_t L = live ? (uint32_t)gbl(a.len)[i] : 0u;
+        uint64_t doff = live ? (a.dst_off ? gbl(a.dst_off)[i] : i * (uint64_t)a.stride) : 0u;
+        uint64_t soff = (COPY && live) ? gbl(a.off)[i] : 0u;
+        if constexpr (ROWS) {
+            // the row guard: the descriptors of a guarded packet are dropped unused
+            if (args.row && r >= args.n_rows) {
+                live = false;
+                L = 0u;
+                doff = soff = 0u;
+            }
+        }
         uint8_t* D = a.dst + doff;
         const uint8_t* S = COPY ? a.src + soff : nullptr;
         const uint32_t T = H + (COPY ? L : 0u);
@@ -116,7 +148,9 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
 
         // 2. the packet's header block in its region, and (2b) its sums' start
         uint8_t* R = regions + j * RS;
-        build_region(R, RS, tmpl, a, i, live, dmis, H + L);
+        if constexpr (ROWS)
+            build_region_rows(R, RS, tmpl, pieces, args.n_pieces, H, i, r, live, dmis, H + L);
+        else build_region(R, RS, tmpl, a, i, live, dmis, H + L);
         if constexpr (SUMS) start_sums(R, a, live, dmis, H + L, acc + j);
 
         // 3. chunk counts -> inclusive prefix over the wave
@@ -125,7 +159,7 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
         wd.src[j] = (uint64_t)(uintptr_t)S;
         wd.pfx[j] = P;
         wd.len[j] = L;
-        wd.mis[j] = dmis | (s_mis << 8);
+        wd.mis[j] = (ROWS && !live) ? GUARDED : dmis | (s_mis << 8);
         // header blocks: every packet takes CP chunk slots, the most any packet
         // of this wave needs (5 for 74 B at 16-B aligned slots, 6 unaligned)
         uint32_t CP = nch;
@@ -159,7 +193,11 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
     // 4. the wave's chunks, 64 per step and UNROLL steps at a time (all their
     //    loads are issued before the first store: bytes in flight): chunk k
     //    belongs to the first packet whose inclusive prefix exceeds k
-    constexpr uint32_t U = COPY ? UNROLL : 2u;  // header blocks: no loads to overlap
+    // header blocks: no loads to overlap.  ROWS: one step fewer in flight: with
+    // UNROLL steps these instantiations took 68 / 66 VGPRs, one workgroup per CU
+    // instead of two (5.11 ms where k_emit<copy, sums> takes 3.61; with one fewer,
+    // 56 / 54 VGPRs and 3.62 ms: profiles/r19_emit_rows_probe.json)
+    constexpr uint32_t U = !COPY ? 2u : ROWS ? UNROLL - 1u : UNROLL;
     for (uint32_t k0 = wg * WAVE * U; k0 < total; k0 += W * WAVE * U) {
         uint32_t q[U], c[U];
         u32x4 own[U], nb[U];
@@ -242,6 +280,7 @@ __global__ __launch_bounds__(Shape<COPY>::BLOCK) void k_emit(EmitArgs a) {
         __syncthreads();
         const uint32_t slot = threadIdx.x / NP, j = threadIdx.x % NP;
         if (slot >= 2u || base + j >= a.n) return;
+        if (ROWS && wd.mis[j] == GUARDED) return;  // nothing parked, nothing to store
         finish_parked(a, fpos, slot, wd.mis[j] & 0xffu, H + wd.len[j],
                       (uint8_t*)(uintptr_t)wd.dst[j],
                       park + slot * NP + j, acc + j);
@@ -261,6 +300,8 @@ static_assert(emit_smem<true>(INGOT_MAX_EMIT_HDR) <= 160u * 1024u, "k_emit<copy>
 static_assert(emit_smem<false>(INGOT_MAX_EMIT_HDR) <= 160u * 1024u, "k_emit LDS > 160 KiB");
 static_assert(emit_smem<true, true>(INGOT_MAX_EMIT_HDR) <= 160u * 1024u,
               "k_emit<copy, sums> LDS > 160 KiB");
+static_assert(emit_smem<true, true>(INGOT_MAX_EMIT_HDR) + sizeof(EmitRowsArgs::p) <= 160u * 1024u,
+              "k_emit<copy, sums, rows> LDS > 160 KiB");
 static_assert(Shape<true>::G == 1 && Shape<true>::BLOCK >= 2 * Shape<true>::NP,
               "sums: one group per block, one lane per parked chunk");
 
@@ -280,6 +321,29 @@ hipError_t go(const EmitArgs& a, hipStream_t s) {
 size_t emit_lds_bytes(const EmitArgs& a) {
     if (a.sums.v4 || a.sums.udp) return emit_smem<true, true>(a.hdr_len);
     return a.src ? emit_smem<true>(a.hdr_len) : emit_smem<false>(a.hdr_len);
+}
+
+// The rows kernels: k_emit<copy>'s launch shape and LDS (sums or not).
+size_t emit_rows_lds_bytes(const EmitRowsArgs& a) {
+    return ((a.e.sums.v4 || a.e.sums.udp) ? emit_smem<true, true>(a.e.hdr_len)
+                                          : emit_smem<true>(a.e.hdr_len)) +
+           sizeof(a.p);
+}
+
+hipError_t launch_emit_rows(const EmitRowsArgs& a, hipStream_t s) {
+    if (a.e.n == 0) return hipSuccess;
+    if (!a.e.src) return hipErrorInvalidValue;
+    constexpr uint32_t NP = Shape<true>::NP;
+    const uint64_t blocks = (a.e.n + NP - 1) / NP;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const size_t smem = emit_rows_lds_bytes(a);
+    if (a.e.sums.v4 || a.e.sums.udp)
+        hipLaunchKernelGGL((k_emit<true, true, true>), dim3((uint32_t)blocks), dim3(Shape<true>::BLOCK),
+                           smem, s, a);
+    else
+        hipLaunchKernelGGL((k_emit<true, false, true>), dim3((uint32_t)blocks), dim3(Shape<true>::BLOCK),
+                           smem, s, a);
+    return hipGetLastError();
 }
 
 hipError_t launch_emit(const EmitArgs& a, hipStream_t s) {

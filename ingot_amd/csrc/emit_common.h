@@ -1,8 +1,9 @@
 // emit_common.h — what the emit kernels share (emit.hip: k_emit; emit_read.hip:
 // k_emit_read).  Helpers: the funnel shift and its DPP neighbour, the
-// predicated edge store, the setters' values, the 16-bit word sums of the
-// fused checksums (sums.h).  Steps of the kernels, below them: the template
-// load, a packet's region and the start of its sums, and a destination
+// predicated edge store, the setters' values (and the per-row operands of the
+// rows kernels), the 16-bit word sums of the fused checksums (sums.h).  Steps
+// of the kernels, below them: the template load, a packet's region (from the
+// sets, or from the rows kernels' pieces) and the start of its sums, and a destination
 // chunk's way out (header merge, UDP share, store, the parked chunks' finish).
 // One copy of each; the kernels keep their descriptors and how a chunk's
 // payload bytes are loaded.
@@ -149,6 +150,82 @@ __device__ __forceinline__ void build_region(uint8_t* R, uint32_t RS, const u32x
         const EmitSet& e = a.sets[s];
         const uint32_t fm = e.bits >= 32 ? 0xffffffffu : ((1u << e.bits) - 1u);
         const uint32_t m = fm << e.rshift, vb = (v[s] & fm) << e.rshift;
+        for (uint32_t k = 0; k < e.nbytes; ++k) {
+            const uint32_t shb = 8u * (e.nbytes - 1u - k);
+            uint8_t& b = R[dmis + e.pos + k];
+            b = (uint8_t)((b & ~(m >> shb)) | ((vb >> shb) & (m >> shb)));
+        }
+    }
+}
+
+// --- ingot_gpu_emit_packets_rows (k_emit's ROWS instantiations) ------------
+// The operand of piece e for packet i, whose row index is r.  `total` as in
+// set_value.  A wire-order piece comes back as the big-endian number the setter loop
+// takes: one load and a byte swap from an aligned table, byte loads otherwise.
+__device__ __forceinline__ uint32_t piece_value(const EmitPiece& e, uint64_t i, uint32_t r,
+                                                uint32_t total) {
+    if (e.source == EP_LENGTH) return total - e.at + (uint32_t)e.add;
+    if (e.source == EP_VALUE) return (uint32_t)e.add;
+    const uint8_t* p = e.values + (e.by ? (uint64_t)r : i) * (uint64_t)e.pitch;
+    switch (e.source) {
+    case EP_U16: return (uint32_t)*gbl((const uint16_t*)p) + (uint32_t)e.add;
+    case EP_U32: return *gbl((const uint32_t*)p) + (uint32_t)e.add;
+    case EP_BE16A: return __builtin_bswap32((uint32_t)*gbl((const uint16_t*)p)) >> 16;
+    case EP_BE32A: return __builtin_bswap32(*gbl((const uint32_t*)p));
+    case EP_BE16: return (uint32_t)gbl(p)[0] << 8 | gbl(p)[1];
+    default:
+        return (uint32_t)gbl(p)[0] << 24 | (uint32_t)gbl(p)[1] << 16 | (uint32_t)gbl(p)[2] << 8 |
+               gbl(p)[3];
+    }
+}
+
+// The pieces into LDS, for every lane of the prologue waves to read at one
+// address: 32 pieces' fields read from the argument block in two unrolled
+// loops made the compiler keep a private copy of the whole block (scratch).
+__device__ __forceinline__ void load_pieces(EmitPiece* P, const EmitRowsArgs& a, uint32_t block) {
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(a.p);
+    for (uint32_t k = threadIdx.x; k < a.n_pieces * (uint32_t)(sizeof(EmitPiece) / 4u); k += block)
+        reinterpret_cast<uint32_t*>(P)[k] = w[k];
+}
+
+// Piece s as every lane of the wave holds it: read from LDS at one address and
+// made scalar, so that its fields sit in SGPRs and the branches on them are
+// the wave's, as they are for the sets of the argument block.
+__device__ __forceinline__ EmitPiece wave_piece(const EmitPiece* P, uint32_t s) {
+    uint32_t w[sizeof(EmitPiece) / 4u];
+#pragma unroll
+    for (uint32_t k = 0; k < sizeof(EmitPiece) / 4u; ++k)
+        w[k] = (uint32_t)__builtin_amdgcn_readfirstlane(
+            (int)reinterpret_cast<const uint32_t*>(P + s)[k]);
+    EmitPiece e;
+    __builtin_memcpy(&e, w, sizeof e);
+    return e;
+}
+
+// Step 2 of the rows kernels: build_region with the pieces P (LDS) in place of
+// the sets; the region's two steps are build_region's.  The first piece's
+// operand is loaded before the template funnel and piece s + 1's before piece
+// s is applied (by packet: coalesced; by row: gathers), so a load's latency
+// overlaps the funnel or the piece before it, in a loop that is not unrolled:
+// no value array, and a prologue of build_region's size.  A packet that is
+// not live (past the batch, or held back by the row guard) loads nothing.
+__device__ __forceinline__ void build_region_rows(uint8_t* R, uint32_t RS, const u32x4* tmpl,
+                                                  const EmitPiece* P, uint32_t n_pieces,
+                                                  uint32_t hdr_len, uint64_t i, uint32_t r,
+                                                  bool live, uint32_t dmis, uint32_t total) {
+    if (!hdr_len || !live) return;
+    uint32_t next = n_pieces ? piece_value(wave_piece(P, 0), i, r, total) : 0u;
+    for (uint32_t m = 0; m < RS / 16u; ++m) {
+        const uint32_t tb = 16u + 16u * m - dmis;  // template byte of region byte 16m (+16)
+        reinterpret_cast<u32x4*>(R)[m] = funnel(tmpl[tb >> 4], tmpl[(tb >> 4) + 1], tb & 15u);
+    }
+#pragma unroll 1
+    for (uint32_t s = 0; s < n_pieces; ++s) {
+        const uint32_t v = next;
+        if (s + 1 < n_pieces) next = piece_value(wave_piece(P, s + 1), i, r, total);
+        const EmitPiece e = wave_piece(P, s);
+        const uint32_t fm = e.bits >= 32 ? 0xffffffffu : ((1u << e.bits) - 1u);
+        const uint32_t m = fm << e.rshift, vb = (v & fm) << e.rshift;
         for (uint32_t k = 0; k < e.nbytes; ++k) {
             const uint32_t shb = 8u * (e.nbytes - 1u - k);
             uint8_t& b = R[dmis + e.pos + k];

@@ -213,6 +213,47 @@ static_assert(sizeof(EmitArgs) <= 4096, "EmitArgs exceeds the 4 KiB kernel-argum
 size_t emit_lds_bytes(const EmitArgs& a);
 hipError_t launch_emit(const EmitArgs& a, hipStream_t s);
 
+// Emit with per-packet and per-row operands (ingot_gpu_emit_packets_rows, k_emit's
+// ROWS instantiations in emit.hip).  api.cpp resolves each
+// ingot_emit_set_rows, in list order, to one piece (a narrow field: EmitSet's
+// geometry) or to big-endian pieces of 4 and 2 bytes (an IPv6 address: 4; a
+// MAC: a 4-byte and a 2-byte one), each with where its operand comes from.
+// `e` is what emit_args / emit_sums made of the header block, with no sets of
+// its own; a block of its own, so the EmitArgs kernels keep theirs.
+enum EmitPieceSource : uint8_t {
+    EP_LENGTH = 0,  // as INGOT_EMIT_LENGTH
+    EP_U16 = 1,     // host-endian u16 at the row (aligned) + add
+    EP_U32 = 2,     // host-endian u32 at the row (aligned) + add
+    EP_VALUE = 3,   // add
+    EP_BE16 = 4,    // 2 bytes of the row in wire order, byte loads
+    EP_BE32 = 5,    // 4 bytes of the row in wire order, byte loads
+    EP_BE16A = 6,   // the same from a 2-byte aligned row: one load
+    EP_BE32A = 7    // the same from a 4-byte aligned row: one load
+};
+struct EmitPiece {
+    uint16_t pos;           // first covering byte of the piece in the header block
+    uint16_t at;            // EP_LENGTH counts the packet's bytes from here
+    uint8_t nbytes, rshift, bits;
+    uint8_t source;         // EmitPieceSource
+    uint8_t by;             // INGOT_BY_PACKET / INGOT_BY_ROW
+    uint8_t _pad[3];
+    int32_t add;
+    uint32_t pitch;         // bytes between rows
+    const uint8_t* values;  // the table + the piece's byte offset in its row
+};
+constexpr uint32_t EMIT_MAX_PIECES = 4 * INGOT_MAX_EMIT_SETS;
+struct EmitRowsArgs {
+    EmitArgs e;
+    const uint32_t* row;  // optional: per-packet row index (the row guard)
+    uint32_t n_rows;
+    uint32_t n_pieces;
+    EmitPiece p[EMIT_MAX_PIECES];
+};
+static_assert(sizeof(EmitPiece) == 32, "EmitPiece is 32 bytes");
+static_assert(sizeof(EmitRowsArgs) <= 4096, "EmitRowsArgs exceeds the 4 KiB kernel-argument limit");
+size_t emit_rows_lds_bytes(const EmitRowsArgs& a);
+hipError_t launch_emit_rows(const EmitRowsArgs& a, hipStream_t s);
+
 // Emit over parse_read's chunk tables (ingot_gpu_emit_packets_read,
 // k_emit_read in emit_read.hip).  `e` is what emit_args / emit_sums made of the
 // header block; e.src is the chunk arena, e.off / e.len / e.stride are unused.

@@ -19,10 +19,14 @@ rewrite over chunked packets (`modify_read`, only with --only: random edit
 lists over cut generator frames against tests/modify_read_model.py, same cap),
 and the emit over chunked packets (`emit_read`, only with --only: every header
 stack in front of cut generator frames with random from / take, whole arenas
-against tests/emit_read_model.py, same cap).
+against tests/emit_read_model.py, same cap), and the emit with per-row
+operands (`emit_rows`, only with --only: every stack and table form of
+tests/emit_rows_cases.py, rows from the flow bins, whole arenas against
+tests/emit_rows_model.py, same cap).
 
     python tools/bigfuzz.py [--frames 4000000] [--seed 1234]
-                            [--only csum|modify_csum|emit_csum|csum_read|modify_read|emit_read]
+                            [--only csum|modify_csum|emit_csum|csum_read|modify_read|emit_read|
+                                    emit_rows]
 """
 from __future__ import annotations
 
@@ -403,6 +407,59 @@ def emit_read_cases(ctx, n, seed, res):
         torch.cuda.empty_cache()
 
 
+def emit_rows_cases(ctx, n, seed, res):
+    """ingot_gpu_emit_packets_rows against tests/emit_rows_model.py, from the
+    generators of tests/emit_rows_cases.py: every stack with every table form
+    in front of generator frames, the row of each packet its flow bin (the
+    uncounted packets are not emitted) and, for 1 packet in 16, a row past
+    the table; whole destination arenas are compared."""
+    import torch
+
+    import ingot_amd
+    from ingot_amd import Chain, GenProfile
+    from tests import emit_rows_cases as rc
+    from tests import emit_rows_model as model
+
+    def dev(a):
+        a = np.ascontiguousarray(a)
+        signed = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32,
+                  np.dtype(np.uint64): np.int64}
+        return torch.from_numpy(a.view(signed.get(a.dtype, a.dtype))).cuda()
+
+    rng = np.random.default_rng(seed)
+    bins = 4096
+    for k, prof in enumerate((GenProfile.MIXED, GenProfile.ADVERSARIAL)):
+        arena, off, lens = ingot_amd.gen_frames(prof, n, seed=seed + 170 + k)
+        flow = ctx.flow_hist(arena, off, lens, Chain.GenericUlp, bins=bins)
+        rows = flow.cpu().numpy().view(np.uint32).copy()
+        rows[rng.random(n) < 1 / 16] = bins
+        live = rows < bins
+        src, s_off, ln = arena.cpu().numpy(), off.cpu().numpy().view(np.uint64), lens.cpu().numpy()
+        d_src, d_off, d_len, d_rows = arena, off, lens, dev(rows)
+        for name in rc.STACKS:
+            for form in rc.FORMS:
+                case = rc.stack(name, form, n, bins, rng)
+                tot = np.where(live, len(case.hdr) + ln.astype(np.int64), 0)
+                gaps = np.where(live, rng.integers(0, 4, n), 0)
+                dst_off = (np.cumsum(np.r_[0, (tot + gaps)[:-1]]) + 5).astype(np.uint64)
+                size = int(dst_off[-1] + tot[-1] + 64)
+                want = np.full(size, 0xA5, np.uint8)
+                model.apply(want, case.hdr, case.host_sets(), case.sums, src, s_off, ln, dst_off,
+                            rows, bins)
+                dst = dev(np.full(size, 0xA5, np.uint8))
+                backing = {key: dev(v) for key, v in case.backing.items()}
+                ctx.emit_packets_rows(case.hdr, case.device_sets(backing), d_src, d_off, d_len, dst,
+                                      dev(dst_off), rows=d_rows, n_rows=bins, sums=case.sums)
+                torch.cuda.synchronize()
+                key = f"emit_rows/{prof.name}/{name}/{form}"
+                res[key] = {"byte_mismatches": int((dst.cpu().numpy() != want).sum()),
+                            "arena_bytes": size, "emitted": int(live.sum()),
+                            "not_emitted": int((~live).sum())}
+                print(key, res[key], flush=True)
+                del dst, backing
+        torch.cuda.empty_cache()
+
+
 def finish(n, seed, t0, res):
     out = {"frames_per_case": n, "seed": seed, "wall_s": round(time.time() - t0, 1),
            "cases": res,
@@ -420,15 +477,17 @@ def main():
                     help="frames per csum case (its reference is a Python model)")
     ap.add_argument("--only", default="",
                     help="'csum' / 'modify_csum' / 'emit_csum' / 'csum_read' / 'modify_read' / "
-                         "'emit_read': run only that case group")
+                         "'emit_read' / 'emit_rows': run only that case group")
     args = ap.parse_args()
-    if args.only in ("csum", "modify_csum", "emit_csum", "csum_read", "modify_read", "emit_read"):
+    if args.only in ("csum", "modify_csum", "emit_csum", "csum_read", "modify_read", "emit_read",
+                     "emit_rows"):
         import ingot_amd
 
         res, t0 = {}, time.time()
         group = {"csum": csum_cases, "modify_csum": modify_csum_cases,
                  "emit_csum": emit_csum_cases, "csum_read": csum_read_cases,
-                 "modify_read": modify_read_cases, "emit_read": emit_read_cases}[args.only]
+                 "modify_read": modify_read_cases, "emit_read": emit_read_cases,
+                 "emit_rows": emit_rows_cases}[args.only]
         group(ingot_amd.Context(0), min(args.frames, args.csum_frames), args.seed, res)
         return finish(min(args.frames, args.csum_frames), args.seed, t0, res)
 

@@ -38,12 +38,32 @@ an empty chunk where the record is not Ok), rows
 checks once that c and d, and e and f, leave identical bytes, and compares the
 rounds' ranges: the new row's maximum against the old row's minimum.
 
+`--rows` measures ingot_gpu_emit_packets_rows instead: the
+same frames and stack, the outer IPv6 destination and Ethernet destination of
+every packet taken from a table, rows
+
+  a  emit_csum          as b above (the UDP sum);
+  b  rows_no_table      the new call with the same narrow sets and no table
+                        (what the new prologue costs by itself);
+  c  rows_by_packet     b + the two wide sets BY_PACKET (n-row tables);
+  d  rows_by_row        the same BY_ROW from a 65,536-row table indexed by
+                        ingot_gpu_flow_hist's bins (uncounted packets take row
+                        0, so that every row of this table emits every packet);
+  dg rows_by_row_guard  d with the bins as they are: uncounted packets are not
+                        emitted;
+  e  emit_modify_rows   today's route to d's bytes: emit_packets_csum, then
+                        ingot_gpu_parse_modify_rows (GENEVE_OVER_V6, the two
+                        wide fields BY_ROW, OUTER_L4), which parses by itself;
+  e3 emit_parse_modify_rows  e with the separate parse of the result between;
+
+checks once that a and b, and c, d and e, leave identical bytes.
+
 `--usage-only` compiles ingot_amd/csrc/emit.hip, emit_read.hip and csum.hip with
 -Rpass-analysis=kernel-resource-usage and writes the kernels' figures (no GPU
 needed); `--usage FILE` attaches such a file to the result.
 
     python tools/emit_csum_probe.py [--frames N] [--reps 5] [--rounds 5] [--read]
-        [--against head] [--usage FILE] [--out profiles/r12_emit_csum_probe.json]
+        [--rows] [--against head] [--usage FILE] [--out profiles/r12_emit_csum_probe.json]
 """
 from __future__ import annotations
 
@@ -69,8 +89,10 @@ def resource_usage() -> dict:
                str(ROOT / "ingot_amd" / "csrc" / src), "-o", "/dev/null"]
         err += subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
     out, cur = {}, None
-    names = {"k_emitILb1ELb1EE": "k_emit<copy, sums>", "k_emitILb1ELb0EE": "k_emit<copy>",
-             "k_emitILb0ELb0EE": "k_emit<headers>", "k_emit_readILb1EE": "k_emit_read<sums>",
+    names = {"k_emitILb1ELb1ELb1EE": "k_emit<copy, sums, rows>",
+             "k_emitILb1ELb0ELb1EE": "k_emit<copy, rows>",
+             "k_emitILb1ELb1ELb0EE": "k_emit<copy, sums>", "k_emitILb1ELb0ELb0EE": "k_emit<copy>",
+             "k_emitILb0ELb0ELb0EE": "k_emit<headers>", "k_emit_readILb1EE": "k_emit_read<sums>",
              "k_emit_readILb0EE": "k_emit_read", "6k_csumE": "k_csum", "11k_csum_readE": "k_csum_read"}
     for line in err.splitlines():
         m = re.search(r"remark: +([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+)", line)
@@ -299,6 +321,93 @@ def child_read(args) -> dict:
             "f1_over_b": round(runs["f1_read_csum_1chunk"]["us"] / runs["b_emit_csum"]["us"], 4)}
 
 
+def child_rows(args) -> dict:
+    import torch
+
+    from ingot_amd import CSUM_OUTER_L4, Chain, EditOp, EmitSource, WideField
+
+    d = setup(args.frames, args.copies)
+    ctx, n, H = d["ctx"], args.frames, d["H"]
+    arena, off, lens, hdr, dst_off = d["arena"], d["off"], d["lens"], d["hdr"], d["dst_off"]
+    sets, sums, bins = d["sets"], d["sums"], 1 << 16
+    g = torch.Generator(device="cuda").manual_seed(2)
+    # one (bins, 32) table: underlay IPv6 at 0, next-hop MAC at 16
+    table = torch.randint(0, 256, (bins, 32), dtype=torch.uint8, device="cuda", generator=g)
+    v6_row, mac_row = table[:, 0:16], table[:, 16:22]
+    flow = ctx.flow_hist(arena, off, lens, Chain.GenericUlp, bins=bins)
+    counted = flow >= 0
+    rows_all = torch.where(counted, flow, torch.zeros_like(flow)).contiguous()
+    v6_pkt = v6_row[rows_all.to(torch.int64)].contiguous()
+    mac_pkt = mac_row[rows_all.to(torch.int64)].contiguous()
+    V6D, MACD, B = WideField.V6_DESTINATION, WideField.ETH_DESTINATION, EmitSource.BYTES
+    by_packet = sets + [(14, V6D, B, 0, v6_pkt), (0, MACD, B, 0, mac_pkt)]
+    by_row = sets + [(14, V6D, B, 0, ("row", v6_row)), (0, MACD, B, 0, ("row", mac_row))]
+    edits = [(1, V6D, EditOp.SET, ("row", v6_row)), (0, MACD, EditOp.SET, ("row", mac_row))]
+    recs = torch.empty((n, 16), dtype=torch.uint8, device="cuda")
+    TUN = Chain.GeneveOverV6Tunnel
+
+    def pick(dst):
+        return d["pick"]() if dst is None else dst
+
+    def emit_csum(dst=None):
+        ctx.emit_packets(hdr, sets, arena, off, lens, pick(dst), dst_off, sums=sums)
+
+    def rows_no_table(dst=None):
+        ctx.emit_packets_rows(hdr, sets, arena, off, lens, pick(dst), dst_off, sums=sums)
+
+    def rows_by_packet(dst=None):
+        ctx.emit_packets_rows(hdr, by_packet, arena, off, lens, pick(dst), dst_off, sums=sums)
+
+    def rows_by_row(dst=None):
+        ctx.emit_packets_rows(hdr, by_row, arena, off, lens, pick(dst), dst_off, rows=rows_all,
+                              n_rows=bins, sums=sums)
+
+    def rows_by_row_guard(dst=None):
+        ctx.emit_packets_rows(hdr, by_row, arena, off, lens, pick(dst), dst_off, rows=flow,
+                              n_rows=bins, sums=sums)
+
+    def emit_modify_rows(dst=None, parse=False):
+        dst = pick(dst)
+        ctx.emit_packets(hdr, sets, arena, off, lens, dst, dst_off, sums=sums)
+        if parse:
+            ctx.parse(dst, dst_off, d["tl"], TUN, out=recs)
+        ctx.parse_modify_rows(dst, dst_off, d["tl"], TUN, edits, rows=rows_all, n_rows=bins,
+                              csum=CSUM_OUTER_L4)
+
+    def emit_parse_modify_rows(dst=None):
+        emit_modify_rows(dst, parse=True)
+
+    x, y = d["dsts"][0], d["dsts"][1 % len(d["dsts"])]
+    same = {}
+    for name, old, new in (("a_equals_b", emit_csum, rows_no_table),
+                           ("c_equals_d", rows_by_packet, rows_by_row),
+                           ("e_equals_d", emit_modify_rows, rows_by_row)):
+        x.fill_(0xA5)
+        y.fill_(0xA5)
+        old(x)
+        new(y)
+        torch.cuda.synchronize()
+        same[name] = bool(torch.equal(x, y)) if x is not y else None
+        if same[name] is False:
+            same[name + "_bytes_differ"] = int((x != y).sum().item())
+    runs = timed({"a_emit_csum": emit_csum, "b_rows_no_table": rows_no_table,
+                  "c_rows_by_packet": rows_by_packet, "d_rows_by_row": rows_by_row,
+                  "dg_rows_by_row_guard": rows_by_row_guard, "e_emit_modify_rows": emit_modify_rows,
+                  "e3_emit_parse_modify_rows": emit_parse_modify_rows}, args.reps, args.rounds)
+    for r in runs.values():
+        r["min"], r["max"] = min(r["rounds"]), max(r["rounds"])
+    us = {k: r["us"] for k, r in runs.items()}
+    return {"frames": n, "hdr_len": H, "payload_bytes": d["payload"], "emitted_bytes": d["total"],
+            "table_rows": bins, "table_pitch": 32, "counted_packets": int(counted.sum().item()),
+            "copies": args.copies, "reps": args.reps, "same_bytes": same, "runs": runs,
+            "rounds_spread_max": max(r["spread"] for r in runs.values()),
+            "b_over_a": round(us["b_rows_no_table"] / us["a_emit_csum"], 4),
+            "c_over_b": round(us["c_rows_by_packet"] / us["b_rows_no_table"], 4),
+            "d_over_c": round(us["d_rows_by_row"] / us["c_rows_by_packet"], 4),
+            "d_over_e": round(us["d_rows_by_row"] / us["e_emit_modify_rows"], 4),
+            "d_max_le_e_min": bool(runs["d_rows_by_row"]["max"] <= runs["e_emit_modify_rows"]["min"])}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=1 << 23)
@@ -312,12 +421,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--child", default=None)
     ap.add_argument("--read", action="store_true", help="the chunked emit's rows (DESIGN 4.12)")
+    ap.add_argument("--rows", action="store_true", help="emit_packets_rows' rows (DESIGN 4.15)")
     args = ap.parse_args()
     if args.usage_only:
         out = resource_usage()
     elif args.child:
         print(json.dumps(child_main(args) if args.child == "main"
                          else child_read(args) if args.child == "read"
+                         else child_rows(args) if args.child == "rows"
                          else child_plain(args.child, args)), flush=True)
         return
     else:
@@ -331,7 +442,7 @@ def main():
                 sys.exit(p.returncode or 1)
             return json.loads(p.stdout.strip().splitlines()[-1])
 
-        out = {"what": __doc__.split("\n\n")[0], **run("read" if args.read else "main")}
+        out = {"what": __doc__.split("\n\n")[0], **run("read" if args.read else "rows" if args.rows else "main")}
         print(json.dumps(out), flush=True)
         if args.against:
             rows = []
