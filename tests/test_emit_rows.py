@@ -64,12 +64,26 @@ def _check(ctx, torch, case, src, off, lens, dst_off, size, rows=None, n_rows=0,
     return got
 
 
+def _check_both(ctx, torch, case, *args, **kw):
+    """_check with the stack's sums (k_emit<true, true, true>) and with none
+    named (k_emit<true, false, true>) -> both arenas."""
+    sums = case.sums
+    assert sums
+    with_sums = _check(ctx, torch, case, *args, **kw)
+    case.sums = None
+    try:
+        return with_sums, _check(ctx, torch, case, *args, **kw)
+    finally:
+        case.sums = sums
+
+
 @pytest.mark.parametrize("form", rc.FORMS)
 @pytest.mark.parametrize("name", rc.STACKS)
 def test_stacks_and_tables(ctx, torch, name, form):
-    """Every stack with every table form: 700 packets (two group boundaries
-    and a ragged tail) over 7 rows, so many packets share a row; guarded
-    packets at lanes 0 and 63 of a subgroup and at the end."""
+    """Every stack with every table form, with its sums and with none: 700
+    packets (two group boundaries and a ragged tail) over 7 rows, so many
+    packets share a row; guarded packets at lanes 0 and 63 of a subgroup and
+    at the end."""
     rng = np.random.default_rng(11 + 10 * rc.STACKS.index(name) + rc.FORMS.index(form))
     n, n_rows = 700, 7
     rows = rc.row_indices(n, n_rows, rng, guarded=(64, 127, 320, 383, n - 1))
@@ -77,35 +91,36 @@ def test_stacks_and_tables(ctx, torch, name, form):
     src, off, ln, dst_off, size = rc.batch(n, len(case.hdr), rng, rows, n_rows)
     assert 65535 in ln[rows < n_rows].tolist() and (n_rows - 1) in rows.tolist()
     assert {int(d) & 15 for d in dst_off[rows < n_rows]} == set(range(16))
-    _check(ctx, torch, case, src, off, ln, dst_off, size, rows, n_rows, (name, form))
+    _check_both(ctx, torch, case, src, off, ln, dst_off, size, rows, n_rows, (name, form))
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 700])
 def test_batch_sizes(ctx, torch, n):
     """Batches that end inside, at and just past a wave and a 256-packet
-    group, indexing a 65,536-row table."""
+    group, indexing a 65,536-row table, with the stack's sums and with none."""
     rng = np.random.default_rng(500 + n)
     n_rows = 65536
     rows = rc.row_indices(n, n_rows, rng)
     for name in ("opte", "v6_udp"):
         case = rc.stack(name, "struct32", n, n_rows, rng)
         src, off, ln, dst_off, size = rc.batch(n, len(case.hdr), rng, rows, n_rows)
-        _check(ctx, torch, case, src, off, ln, dst_off, size, rows, n_rows, (name, n))
+        _check_both(ctx, torch, case, src, off, ln, dst_off, size, rows, n_rows, (name, n))
         # and without a row array: BY_PACKET tables only
         if name == "v6_udp":
             src, off, ln, dst_off, size = rc.batch(n, len(case.hdr), rng)
-            _check(ctx, torch, case, src, off, ln, dst_off, size, tag=(name, n, "no rows"))
+            _check_both(ctx, torch, case, src, off, ln, dst_off, size, tag=(name, n, "no rows"))
 
 
 @pytest.mark.parametrize("n_rows", [1, 7, 65536])
 def test_row_counts(ctx, torch, n_rows):
+    """1, 7 and 65,536 rows, with the stack's sums and with none."""
     rng = np.random.default_rng(600 + n_rows % 97)
     n = 300
     rows = rc.row_indices(n, n_rows, rng, guarded=(5, 6))
     for name in ("opte", "geneve_v4"):
         case = rc.stack(name, "dense", n, n_rows, rng)
         src, off, ln, dst_off, size = rc.batch(n, len(case.hdr), rng, rows, n_rows)
-        _check(ctx, torch, case, src, off, ln, dst_off, size, rows, n_rows, (name, n_rows))
+        _check_both(ctx, torch, case, src, off, ln, dst_off, size, rows, n_rows, (name, n_rows))
 
 
 GUARDS = {
@@ -122,16 +137,18 @@ GUARDS = {
 def test_row_guard(ctx, torch, where):
     """Packets whose row is n_rows or INGOT_ROW_NONE are not emitted: their
     neighbours, packed against each other with no gap, keep their edge bytes,
-    and descriptors that point outside the arenas are never used."""
+    and descriptors that point outside the arenas are never used; with the
+    stack's sums and with none."""
     rng = np.random.default_rng(len(where) + 700)
     n, n_rows = 700, 7
     rows = rc.row_indices(n, n_rows, rng, guarded=GUARDS[where])
     for name in ("opte", "geneve_v4"):
         case = rc.stack(name, "dense", n, n_rows, rng)
         src, off, ln, dst_off, size = rc.batch(n, len(case.hdr), rng, rows, n_rows)
-        got = _check(ctx, torch, case, src, off, ln, dst_off, size, rows, n_rows, (name, where))
+        both = _check_both(ctx, torch, case, src, off, ln, dst_off, size, rows, n_rows,
+                           (name, where))
         if where == "all":
-            assert (got == 0xA5).all()
+            assert all((got == 0xA5).all() for got in both)
 
 
 @pytest.mark.parametrize("first", ["wide", "narrow"])
