@@ -41,7 +41,8 @@ extern "C" {
 /* 4: ingot_gpu_checksum_verify / ingot_gpu_checksum_fill (ingot_csum);
  *    ingot_gpu_parse_modify_csum, ingot_gpu_checksum_verify_read / _fill_read,
  *    ingot_gpu_parse_read_modify / ingot_gpu_parse_read_modify_csum,
- *    ingot_gpu_parse_modify_rows, ingot_gpu_flow_table_* /
+ *    ingot_gpu_parse_modify_rows, ingot_gpu_parse_read_modify_rows,
+ *    ingot_gpu_flow_table_* /
  *    ingot_gpu_flow_key_hash (added calls: the number stays).
  * 3: ingot_gpu_comm_wrap (borrow the host's RCCL communicator).
  * 2: ingot_gpu_comm_* / ingot_gpu_flow_hist_allreduce (config 5's reduce);
@@ -1278,10 +1279,10 @@ int ingot_gpu_parse_modify_csum(ingot_gpu_ctx* ctx, uint8_t* d_arena,
  *   5. a NULL arena, the slots' stride / alignment rules, d_off without d_len.
  *
  * Out of scope: the slot-ring kernel (slots >= 64 B without a length array
- * run the plain per-tile kernel here, whatever INGOT_TUNE_PIPELINE says); the
- * chunked form (ingot_gpu_parse_read_modify takes no tables); ops other than
- * SET on wide fields; wide fields in ingot_edit (the emit takes them in
- * ingot_gpu_emit_packets_rows, below).
+ * run the plain per-tile kernel here, whatever INGOT_TUNE_PIPELINE says); ops
+ * other than SET on wide fields; wide fields in ingot_edit (the emit takes them
+ * in ingot_gpu_emit_packets_rows, the chunked rewrite in
+ * ingot_gpu_parse_read_modify_rows, both below).
  * ------------------------------------------------------------------------- */
 enum ingot_wide_field {            /* only valid in ingot_edit_rows.field */
     INGOT_FW_ETH_DESTINATION = 64, /* ethernet.rs, 6 B at +0  */
@@ -1477,6 +1478,71 @@ int ingot_gpu_parse_read_modify_csum(ingot_gpu_ctx* ctx, uint8_t* d_arena,
                                      const uint64_t* d_seg_off, const uint16_t* d_seg_len,
                                      const uint32_t* d_pkt_seg, uint64_t n, int chain,
                                      const ingot_edit* edits, uint32_t n_edits,
+                                     uint32_t what, ingot_rec* d_out, uint16_t* d_chunk,
+                                     void* stream);
+
+/* ---------------------------------------------------------------------------
+ * The rewrite over chunked packets with per-packet operands and the address
+ * setters: ingot_gpu_parse_read_modify_csum's chunk lists with
+ * ingot_gpu_parse_modify_rows' edits.  A NAT address, a next-hop MAC or a
+ * tunnel endpoint per flow for packets held as an mblk chain or in a
+ * header-split ring, without pulling them up; and, after
+ * ingot_gpu_emit_headers, the outer IPv6 destination, MAC and VNI per row over
+ * the header slot + the untouched source frame, with the outer UDP sum updated
+ * in place.  No new struct or enum: ingot_edit_rows, ingot_wide_field,
+ * ingot_edit_source, ingot_edit_by and INGOT_ROW_NONE are
+ * ingot_gpu_parse_modify_rows'.  Build-defined;
+ * tests/modify_read_rows_model.py is the definition.
+ *
+ * Tables, parse, records, d_chunk are ingot_gpu_parse_read_modify's: the CSR
+ * tables of ingot_gpu_parse_read; d_out and d_chunk are both optional and get,
+ * byte for byte, what ingot_gpu_parse_read writes; the parse sees the bytes
+ * before the edits.
+ *
+ * Edits.  Fields (the wide ones too), sources, `by`, pitch, ops and order are
+ * ingot_gpu_parse_modify_rows'; they are applied to packets whose record is Ok
+ * at the record's logical offsets (the chunks concatenated), as
+ * ingot_gpu_parse_read_modify applies them.  A wide field lies inside its
+ * header and every header parse_read accepted lies in one chunk, so each wide
+ * field lies in one chunk.
+ *
+ * Row guard.  With d_row given, a packet whose d_row[i] >= n_rows has no byte
+ * written and no table read; its record and chunk index are still written.
+ * With d_row NULL no edit may be BY_ROW (EINVAL) and n_rows is ignored.
+ *
+ * Checksums.  what == 0: none.  Otherwise the sums, their covered ranges (the
+ * IPv6 pseudo-header and the tunnel chain's ranges included), the UDP rules
+ * and the refused fields are ingot_gpu_parse_modify_rows'.  A byte's place in
+ * its 16-bit word is the parity of its logical offset, and inner sums come
+ * before OUTER_L4, as in ingot_gpu_parse_read_modify_csum.
+ *
+ * Bytes written: exactly the covering bytes of each applied edit and the two
+ * bytes of each updated sum.  A store may be 1, 2 or 4 bytes wide and never
+ * covers a byte outside the field it writes.  Gaps between chunks, other
+ * packets' chunks and payload chunks are not stored to at all.
+ *
+ * Aliasing: ingot_gpu_parse_read_modify's rule.  The tables and d_row are only
+ * read; they may be shared between concurrent calls.
+ *
+ * EINVAL, all checked before any device work, in this order:
+ *   1. checks 1 to 3 of ingot_gpu_parse_modify_rows (ctx, chain, the list; per
+ *      edit; `what`);
+ *   2. n == 0 succeeds;
+ *   3. a NULL d_arena or any NULL chunk table.
+ *
+ * Results never depend on tuning knobs; INGOT_TUNE_READ_PLAN 1 and an arena in
+ * mapped host memory select the 4-piece window, as in
+ * ingot_gpu_parse_read_modify.
+ *
+ * Out of scope: the dense (offset << 16) | length table; the d_first and lazy
+ * forms of parse_read; ops other than SET on wide fields; the C++ mirror
+ * (ingot_amd.hpp).
+ * ------------------------------------------------------------------------- */
+int ingot_gpu_parse_read_modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena,
+                                     const uint64_t* d_seg_off, const uint16_t* d_seg_len,
+                                     const uint32_t* d_pkt_seg, uint64_t n, int chain,
+                                     const ingot_edit_rows* edits, uint32_t n_edits,
+                                     const uint32_t* d_row, uint32_t n_rows,
                                      uint32_t what, ingot_rec* d_out, uint16_t* d_chunk,
                                      void* stream);
 

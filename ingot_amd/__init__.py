@@ -608,6 +608,20 @@ class Context:
         del keep
         return out
 
+    def _chunk_tables(self, arena, seg_off, seg_len, pkt_seg, out, chunk) -> int:
+        """The chunk tables and optional outputs of the chunked rewrites,
+        validated on the host -> the number of packets."""
+        n = pkt_seg.numel() - 1
+        self._arg("arena", arena, _U8)
+        self._arg("pkt_seg", pkt_seg, _U32, n + 1)
+        self._arg("seg_off", seg_off, _U64)
+        self._arg("seg_len", seg_len, _U16, seg_off.numel())
+        self._arg("out", out, _U8, n * REC_BYTES, optional=True)
+        self._arg("chunk", chunk, _U16, n, optional=True)
+        self._on_device(arena=arena, seg_off=seg_off, seg_len=seg_len, pkt_seg=pkt_seg, out=out,
+                        chunk=chunk)
+        return n
+
     def parse_read_modify(self, arena, seg_off, seg_len, pkt_seg, chain: Chain, edits,
                           csum: int = 0, out=None, chunk=None, stream=None):
         """parse_read, then ingot's setters in place over the chunk lists
@@ -619,16 +633,8 @@ class Context:
         csum != 0 (CSUM_L3 | CSUM_L4 | CSUM_OUTER_L4): the same launch also
         updates those checksums from the bytes the edits changed (RFC 1624,
         ingot_gpu_parse_read_modify_csum)."""
-        n = pkt_seg.numel() - 1
-        self._arg("arena", arena, _U8)
-        self._arg("pkt_seg", pkt_seg, _U32, n + 1)
-        self._arg("seg_off", seg_off, _U64)
-        self._arg("seg_len", seg_len, _U16, seg_off.numel())
-        self._arg("out", out, _U8, n * REC_BYTES, optional=True)
-        self._arg("chunk", chunk, _U16, n, optional=True)
+        n = self._chunk_tables(arena, seg_off, seg_len, pkt_seg, out, chunk)
         e = edits_array(edits)
-        self._on_device(arena=arena, seg_off=seg_off, seg_len=seg_len, pkt_seg=pkt_seg, out=out,
-                        chunk=chunk)
         args = (self._h, _ptr(arena), _ptr(seg_off), _ptr(seg_len), _ptr(pkt_seg), n, int(chain),
                 e.ctypes.data_as(ctypes.c_void_p), len(e))
         tail = (_ptr(out), _ptr(chunk), _stream(stream, self.device))
@@ -638,6 +644,28 @@ class Context:
         else:
             _lib.check(self._lib.ingot_gpu_parse_read_modify(*args, *tail),
                        "ingot_gpu_parse_read_modify")
+        return out, chunk
+
+    def parse_read_modify_rows(self, arena, seg_off, seg_len, pkt_seg, chain: Chain, edits,
+                               rows=None, n_rows: int = 0, csum: int = 0, out=None, chunk=None,
+                               stream=None):
+        """parse_read_modify with per-packet operands and the MAC / IPv6
+        address setters (ingot_gpu_parse_read_modify_rows): the chunk tables,
+        `out` and `chunk` are parse_read_modify's, the `edits` tuples, their
+        operand forms, `rows` / `n_rows` (the row guard) and `csum` are
+        parse_modify_rows'.  Returns (out, chunk)."""
+        n = self._chunk_tables(arena, seg_off, seg_len, pkt_seg, out, chunk)
+        self._arg("rows", rows, _U32, n, optional=True)
+        if rows is not None and (n_rows < 0 or n_rows > 0xFFFFFFFF):
+            raise ValueError("n_rows must fit 32 bits")
+        e, keep = self._edit_rows(edits, n, rows, int(n_rows))
+        self._on_device(rows=rows)
+        _lib.check(self._lib.ingot_gpu_parse_read_modify_rows(
+            self._h, _ptr(arena), _ptr(seg_off), _ptr(seg_len), _ptr(pkt_seg), n, int(chain),
+            e.ctypes.data_as(ctypes.c_void_p), len(e), _ptr(rows), int(n_rows), int(csum),
+            _ptr(out), _ptr(chunk), _stream(stream, self.device)),
+            "ingot_gpu_parse_read_modify_rows")
+        del keep
         return out, chunk
 
     def _emit_sets(self, sets, n: int):

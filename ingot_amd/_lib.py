@@ -126,6 +126,11 @@ SIGNATURES = {
         [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, c_u8p, c_u64, ctypes.c_int, c_u8p,
          ctypes.c_uint32, ctypes.c_uint32, c_u8p, c_u8p, ctypes.c_void_p],
     ),
+    "ingot_gpu_parse_read_modify_rows": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_u8p, c_u8p, c_u8p, c_u8p, c_u64, ctypes.c_int, c_u8p,
+         ctypes.c_uint32, c_u8p, ctypes.c_uint32, ctypes.c_uint32, c_u8p, c_u8p, ctypes.c_void_p],
+    ),
     "ingot_gpu_emit_packets": (
         ctypes.c_int,
         [ctypes.c_void_p, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint32, c_u8p, c_u8p, c_u8p,

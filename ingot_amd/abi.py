@@ -349,7 +349,7 @@ def edits_array(edits) -> np.ndarray:
 
 class WideField(enum.IntEnum):
     """enum ingot_wide_field: the 6- and 16-byte setter targets, valid only in
-    ingot_edit_rows (ingot_gpu_parse_modify_rows)."""
+    ingot_edit_rows (ingot_gpu_parse_modify_rows, ingot_gpu_parse_read_modify_rows)."""
 
     ETH_DESTINATION = 64
     ETH_SOURCE = 65

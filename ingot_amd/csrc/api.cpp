@@ -724,16 +724,16 @@ int wide_feeds(int chain, const ingot_edit_rows& e, uint32_t what) {
     return (int)f;
 }
 
-// ingot_gpu_parse_modify_rows: every argument is checked before any device
-// work, in the order the header gives.
-int modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off,
-                const uint16_t* d_len, uint32_t stride, uint64_t n, int chain,
-                const ingot_edit_rows* edits, uint32_t n_edits, const uint32_t* d_row,
-                uint32_t n_rows, uint32_t what, ingot_rec* d_out, void* stream) {
+// The ingot_edit_rows list of ingot_gpu_parse_modify_rows and
+// ingot_gpu_parse_read_modify_rows -> the kernels' pieces, with the sums each
+// feeds: checks 1 to 3 of the header's list, in its order.  `a` comes in
+// zeroed; the frames or chunk tables are the caller's to fill.
+int resolve_edit_rows(const ingot_gpu_ctx* ctx, int chain, const ingot_edit_rows* edits,
+                      uint32_t n_edits, const uint32_t* d_row, uint32_t n_rows, uint32_t what,
+                      ingot_gpu::ModifyRowsArgs& a) {
     using namespace ingot_gpu;
     if (!ctx || !chain_ok(chain) || n_edits > INGOT_MAX_EDITS || (n_edits && !edits))
         return INGOT_GPU_EINVAL;
-    ModifyRowsArgs a{};
     uint32_t np = 0;
     for (uint32_t k = 0; k < n_edits; ++k) {
         const ingot_edit_rows& e = edits[k];
@@ -800,6 +800,21 @@ int modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off,
             for (uint32_t j = 0; j < pieces; ++j) a.e[np++].feeds = (uint8_t)f;
         }
     }
+    a.row = d_row;
+    a.n_rows = n_rows;
+    a.what = what;
+    return INGOT_GPU_SUCCESS;
+}
+
+// ingot_gpu_parse_modify_rows: every argument is checked before any device
+// work, in the order the header gives.
+int modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off,
+                const uint16_t* d_len, uint32_t stride, uint64_t n, int chain,
+                const ingot_edit_rows* edits, uint32_t n_edits, const uint32_t* d_row,
+                uint32_t n_rows, uint32_t what, ingot_rec* d_out, void* stream) {
+    using namespace ingot_gpu;
+    ModifyRowsArgs a{};
+    if (int e = resolve_edit_rows(ctx, chain, edits, n_edits, d_row, n_rows, what, a)) return e;
     if (n == 0) return INGOT_GPU_SUCCESS;
     if (!d_arena) return INGOT_GPU_EINVAL;
     int layout = LAYOUT_INDEXED;
@@ -811,11 +826,26 @@ int modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_off,
     }
     if (int e = enter(ctx)) return e;
     a.p = ParseArgs{d_arena, d_off, d_len, stride, n, d_out};
-    a.row = d_row;
-    a.n_rows = n_rows;
-    a.what = what;
     return from_hip(launch_modify_rows(a, layout, chain, tuning_for(ctx, d_arena),
                                        (hipStream_t)stream));
+}
+
+// ingot_gpu_parse_read_modify_rows: the same edit list over parse_read's CSR
+// chunk tables.
+int read_modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena, const uint64_t* d_seg_off,
+                     const uint16_t* d_seg_len, const uint32_t* d_pkt_seg, uint64_t n, int chain,
+                     const ingot_edit_rows* edits, uint32_t n_edits, const uint32_t* d_row,
+                     uint32_t n_rows, uint32_t what, ingot_rec* d_out, uint16_t* d_chunk,
+                     void* stream) {
+    using namespace ingot_gpu;
+    ModifyRowsArgs a{};
+    if (int e = resolve_edit_rows(ctx, chain, edits, n_edits, d_row, n_rows, what, a)) return e;
+    if (n == 0) return INGOT_GPU_SUCCESS;
+    if (!d_arena || !d_seg_off || !d_seg_len || !d_pkt_seg) return INGOT_GPU_EINVAL;
+    if (int e = enter(ctx)) return e;
+    a.p = ParseArgs{d_arena, d_seg_off, d_seg_len, 0, n, d_out, d_pkt_seg, d_chunk};
+    return from_hip(launch_read_modify_rows(a, chain, tuning_for(ctx, d_arena),
+                                            (hipStream_t)stream));
 }
 
 // ingot_gpu_parse_read_modify (what == 0) and ingot_gpu_parse_read_modify_csum:
@@ -881,6 +911,16 @@ int ingot_gpu_parse_read_modify_csum(ingot_gpu_ctx* ctx, uint8_t* d_arena,
     if (!csum_what_ok(what, chain)) return INGOT_GPU_EINVAL;
     return read_modify(ctx, d_arena, d_seg_off, d_seg_len, d_pkt_seg, n, chain, edits, n_edits,
                        what, d_out, d_chunk, stream);
+}
+
+int ingot_gpu_parse_read_modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena,
+                                     const uint64_t* d_seg_off, const uint16_t* d_seg_len,
+                                     const uint32_t* d_pkt_seg, uint64_t n, int chain,
+                                     const ingot_edit_rows* edits, uint32_t n_edits,
+                                     const uint32_t* d_row, uint32_t n_rows, uint32_t what,
+                                     ingot_rec* d_out, uint16_t* d_chunk, void* stream) {
+    return read_modify_rows(ctx, d_arena, d_seg_off, d_seg_len, d_pkt_seg, n, chain, edits,
+                            n_edits, d_row, n_rows, what, d_out, d_chunk, stream);
 }
 
 }  // extern "C"

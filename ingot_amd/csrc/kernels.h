@@ -370,6 +370,9 @@ hipError_t launch_modify_rows(const ModifyRowsArgs& a, int layout_kind, int chai
 hipError_t launch_read_modify(const ModifyArgs& a, int chain, const Tuning& t, hipStream_t s);
 hipError_t launch_read_modify_csum(const ModifyCsumArgs& a, int chain, const Tuning& t,
                                    hipStream_t s);
+// The same with per-packet operands (ingot_gpu_parse_read_modify_rows, read.hip).
+hipError_t launch_read_modify_rows(const ModifyRowsArgs& a, int chain, const Tuning& t,
+                                   hipStream_t s);
 bool tuning_valid(int key, int value);
 
 }  // namespace ingot_gpu

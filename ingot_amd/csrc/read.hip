@@ -2,7 +2,8 @@
 // ingot-macros/src/parse.rs:511-537): the k_parse_read kernel with the header
 // chunks staged in LDS (SegFrameP) and its launcher; DESIGN.md §1b.  And the
 // rewrite over chunk lists (ingot_gpu_parse_read_modify*): k_parse_read_modify
-// and its launchers; DESIGN.md §4.11.
+// and its launchers; DESIGN.md §4.11, and §4.16 for per-packet operands
+// (ingot_gpu_parse_read_modify_rows).
 #include "walk.h"
 
 namespace ingot_gpu {
@@ -301,6 +302,64 @@ __device__ __forceinline__ void put_byte(const ChunkView<SF>& f, EditSink&, uint
         gbl_mut(const_cast<uint8_t*>(f.f.arena))[f.coff + (i - f.cstart)] = v;
 }
 
+// The whole-byte SET of the rows kernel (ingot_gpu_parse_read_modify_rows): a
+// piece with op SET, rshift 0 and bits = 8 * nbytes replaces its covering bytes
+// outright — every piece of a MAC or IPv6 address, the 16- and 32-bit narrow
+// SETs, the hop limit.  Through apply_edit such a piece costs nbytes located
+// byte loads and nbytes located byte stores; here the chunk is located once
+// (by the caller), the old bytes are loaded only when a selected sum covers
+// them, and a piece whose address is a multiple of its size goes out as one
+// store.  The loads and stores go through gbl / gbl_mut like the byte path's
+// and their types may alias anything, so a later edit of the packet and
+// csum_finish read what was stored here.  Returns apply_edit<true>'s term.
+// INGOT_READ_ROWS_FAST_SET 0 compiles the path out (every piece through
+// apply_edit: the A/B of DESIGN.md §4.16; not a tuning knob).
+#ifndef INGOT_READ_ROWS_FAST_SET
+#define INGOT_READ_ROWS_FAST_SET 1
+#endif
+typedef __attribute__((address_space(1), may_alias)) uint16_t g_u16;
+typedef __attribute__((address_space(1), may_alias)) uint32_t g_u32;
+
+__device__ __forceinline__ bool whole_byte_set(const Edit& e) {
+    return e.op == INGOT_OP_SET && e.rshift == 0u && e.bits == 8u * e.nbytes;
+}
+
+// `f` has located logical bytes [at, at + e.nbytes) in one chunk.
+template <class SF>
+__device__ __forceinline__ uint32_t set_located(const ChunkView<SF>& f, uint32_t at,
+                                                const Edit& e, bool fed) {
+    const uint32_t n = e.nbytes;
+    uint8_t* p = const_cast<uint8_t*>(f.f.arena) + f.coff + (at - f.cstart);
+    const uint32_t w_new = n >= 4u ? e.value : e.value & ((1u << (8u * n)) - 1u);
+    const bool whole = (n == 4u || n == 2u) && ((uintptr_t)p & (n - 1u)) == 0u;
+    uint32_t w_old = 0;
+    // (the wide types are put on after gbl / gbl_mut: a template argument
+    // drops may_alias)
+    if (whole && n == 4u) {
+        if (fed) w_old = __builtin_bswap32(*reinterpret_cast<const g_u32*>(gbl(p)));
+        *reinterpret_cast<g_u32*>(gbl_mut(p)) = __builtin_bswap32(w_new);
+    } else if (whole) {
+        if (fed) w_old = __builtin_bswap32(*reinterpret_cast<const g_u16*>(gbl(p))) >> 16;
+        *reinterpret_cast<g_u16*>(gbl_mut(p)) = (uint16_t)(__builtin_bswap32(w_new) >> 16);
+    } else {
+        if (fed)
+            for (uint32_t j = 0; j < n; ++j) w_old = (w_old << 8) | gbl(p)[j];
+        for (uint32_t j = 0; j < n; ++j) gbl_mut(p)[j] = (uint8_t)(w_new >> (8u * (n - 1u - j)));
+    }
+    return fed ? csum_term(at, n, w_old, w_new) : 0u;
+}
+
+// One piece of the rows kernel: the located SET above, or the shared setter.
+template <class SF>
+__device__ __forceinline__ uint32_t rows_edit(const ChunkView<SF>& f, EditSink& sink, uint32_t h,
+                                              const Edit& e, uint32_t feeds) {
+#if INGOT_READ_ROWS_FAST_SET
+    if (whole_byte_set(e) && f.locate(h + e.byte0, e.nbytes))
+        return set_located(f, h + e.byte0, e, feeds != 0u);
+#endif
+    return apply_edit<true>(f, sink, h, e);
+}
+
 // The rewrite over chunk lists (ingot_gpu_parse_read_modify, ARGS = ModifyArgs;
 // ingot_gpu_parse_read_modify_csum, ARGS = ModifyCsumArgs): k_parse_read's
 // record path over the CSR tables (three prefetched descriptors, the window
@@ -320,8 +379,16 @@ __device__ __forceinline__ void put_byte(const ChunkView<SF>& f, EditSink&, uint
 // twice, a checksum field set by an edit and then updated), and every store
 // is a byte store inside the one chunk that holds the header: no neighbouring
 // byte, which may belong to a packet another lane is editing, is written.
+//
+// ARGS = ModifyRowsArgs (ingot_gpu_parse_read_modify_rows): each piece's
+// operand from a device table, by packet or by the packet's row, behind the
+// row guard, as in k_parse's rows mode; `what` is a run-time value (0: no sum
+// is touched), so there is one kernel per window and chain.  Whole-byte SET
+// pieces take rows_edit's located path (above): their stores are 1, 2 or 4
+// bytes wide and still lie inside the field they write.
 template <int CS0, int CHAIN, class ARGS>
 __global__ __launch_bounds__(BLOCK) void k_parse_read_modify(ARGS args) {
+    constexpr bool ROWS = std::is_same<ARGS, ModifyRowsArgs>::value;
     constexpr bool CSUM = std::is_same<ARGS, ModifyCsumArgs>::value;
     const ParseArgs& a = base_args(args);
     using FR = SegFrameP<CS0, false, 3, false>;
@@ -351,6 +418,17 @@ __global__ __launch_bounds__(BLOCK) void k_parse_read_modify(ARGS args) {
         fr.l1 = nseg > 2 ? a.len[s0 + 1] : 0u;
         fr.l2 = nseg > 3 ? a.len[s0 + 2] : 0u;
         fr.l3 = nseg > 4 ? a.len[s0 + 3] : 0u;
+        // ROWS: the packet's row, loaded with the descriptors so that the
+        // gather of its table rows does not wait for two dependent round
+        // trips; the row guard is part of "edit this packet" (k_parse's)
+        [[maybe_unused]] uint32_t row = 0;
+        [[maybe_unused]] bool edit = valid;
+        if constexpr (ROWS) {
+            if (valid && args.row) {
+                row = args.row[i];
+                edit = row < args.n_rows;  // INGOT_ROW_NONE too
+            }
+        }
         // chunk 0's window from the piece holding its byte SKIP, packet-major
         // (k_parse_read's staging)
         constexpr uint32_t SKIP = INGOT_REC_SKIP;
@@ -412,24 +490,41 @@ __global__ __launch_bounds__(BLOCK) void k_parse_read_modify(ARGS args) {
         if (valid && a.chunk) a.chunk[i] = (uint16_t)fr.k;
         // the setters, in order, on packets parsed Ok (no store for any
         // other packet, nor for lanes past n)
-        if (valid && r.status == INGOT_OK) {
+        if (edit && r.status == INGOT_OK) {
             const ChunkView<FR> cv(fr);
             EditSink sink{};  // (unused by this view's put_byte)
-            [[maybe_unused]] typename std::conditional<CSUM, CsumAcc, NoCsum>::type acc;
-            const ModifyArgs& m = edit_args(args);
-            for (uint32_t k = 0; k < m.n_edits; ++k) {
-                const Edit e = m.e[k];
-                uint32_t h;
-                if (header_at<CHAIN>(r, e.layer, e.kind, e.index, h)) {
-                    if constexpr (CSUM)
-                        csum_feed(acc, args.feeds[k], r, apply_edit<true>(cv, sink, h, e));
-                    else
-                        apply_edit(cv, sink, h, e);
+            [[maybe_unused]] typename std::conditional<CSUM || ROWS, CsumAcc, NoCsum>::type acc;
+            if constexpr (ROWS) {
+                for (uint32_t k = 0; k < args.n_pieces; ++k) {
+                    const RowPiece& pc = args.e[k];
+                    Edit e = pc.e;
+                    uint32_t h;
+                    // (no table is read for a piece that is not applied)
+                    if (header_at<CHAIN>(r, e.layer, e.kind, e.index, h)) {
+                        e.value = row_operand(pc, pc.by == INGOT_BY_ROW ? (uint64_t)row : i);
+                        csum_feed(acc, pc.feeds, r, rows_edit(cv, sink, h, e, pc.feeds));
+                    }
                 }
+                if (args.what)
+                    csum_finish<CHAIN>(cv, r, args.what, acc,
+                                       [&](uint32_t at, uint8_t v) { put_byte(cv, sink, at, v); });
+            } else {
+                const ModifyArgs& m = edit_args(args);
+                for (uint32_t k = 0; k < m.n_edits; ++k) {
+                    const Edit e = m.e[k];
+                    uint32_t h;
+                    if (header_at<CHAIN>(r, e.layer, e.kind, e.index, h)) {
+                        if constexpr (CSUM)
+                            csum_feed(acc, args.feeds[k], r, apply_edit<true>(cv, sink, h, e));
+                        else
+                            apply_edit(cv, sink, h, e);
+                    }
+                }
+                if constexpr (CSUM)
+                    csum_finish<CHAIN>(cv, r, args.what, acc, [&](uint32_t at, uint8_t v) {
+                        put_byte(cv, sink, at, v);
+                    });
             }
-            if constexpr (CSUM)
-                csum_finish<CHAIN>(cv, r, args.what, acc,
-                                   [&](uint32_t at, uint8_t v) { put_byte(cv, sink, at, v); });
         }
     }
 }
@@ -438,9 +533,15 @@ __global__ __launch_bounds__(BLOCK) void k_parse_read_modify(ARGS args) {
 // INGOT_TUNE_READ_PLAN 1, or an arena in mapped host memory, = 4 pieces; else
 // the line-completing 3 to 5), its record stores and its grid.
 template <class ARGS>
+ParseArgs& tables_of(ARGS& a) {
+    return edit_args(a).p;
+}
+ParseArgs& tables_of(ModifyRowsArgs& a) { return a.p; }  // (no ModifyArgs inside)
+
+template <class ARGS>
 hipError_t launch_read_modify_as(const ARGS& args, int chain, const Tuning& t, hipStream_t s) {
     ARGS b = args;
-    ParseArgs& p = edit_args(b).p;
+    ParseArgs& p = tables_of(b);
     if (p.n == 0) return hipSuccess;
     p.policy = t.cache_policy == 0 ? 2u : (uint32_t)t.cache_policy & 0x1fbu;  // launch_parse's
     const uint32_t g = grid_for(p.n, t.max_blocks);
@@ -475,6 +576,11 @@ hipError_t launch_read_modify(const ModifyArgs& a, int chain, const Tuning& t, h
 }
 
 hipError_t launch_read_modify_csum(const ModifyCsumArgs& a, int chain, const Tuning& t,
+                                   hipStream_t s) {
+    return launch_read_modify_as(a, chain, t, s);
+}
+
+hipError_t launch_read_modify_rows(const ModifyRowsArgs& a, int chain, const Tuning& t,
                                    hipStream_t s) {
     return launch_read_modify_as(a, chain, t, s);
 }

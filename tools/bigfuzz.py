@@ -22,11 +22,14 @@ stack in front of cut generator frames with random from / take, whole arenas
 against tests/emit_read_model.py, same cap), and the emit with per-row
 operands (`emit_rows`, only with --only: every stack and table form of
 tests/emit_rows_cases.py, rows from the flow bins, whole arenas against
-tests/emit_rows_model.py, same cap).
+tests/emit_rows_model.py, same cap), and the rewrite over chunked packets with
+per-packet operands (`modify_read_rows`, only with --only: modify_read's five
+sets with random mixed lists, tables, guards and every `what`, against
+tests/modify_read_rows_model.py, same cap).
 
     python tools/bigfuzz.py [--frames 4000000] [--seed 1234]
                             [--only csum|modify_csum|emit_csum|csum_read|modify_read|emit_read|
-                                    emit_rows]
+                                    emit_rows|modify_read_rows]
 """
 from __future__ import annotations
 
@@ -343,6 +346,85 @@ def modify_read_cases(ctx, n, seed, res):
         torch.cuda.empty_cache()
 
 
+def modify_read_rows_cases(ctx, n, seed, res):
+    """ingot_gpu_parse_read_modify_rows over modify_read's five sets (the same
+    generator profiles x chains, cut by tests/csum_read_cases.py's `cut`), with
+    the random mixed lists of tests/modify_read_rows_cases.py (wide and narrow
+    fields, every op, VALUE / U16 / U32 / BYTES operands by packet and by row),
+    random guards and every `what` of the chain in turn, 0 included, against
+    tests/modify_read_rows_model.py: the whole arena, the records and the chunk
+    indices.  Every other case has its sums filled first."""
+    import torch
+
+    import ingot_amd
+    from ingot_amd import Chain, GenProfile
+    from ingot_amd.abi import ROW_NONE
+    from tests import csum_read_cases as cases
+    from tests import modify_read_model as mrm
+    from tests import modify_read_rows_cases as rc2
+    from tests import modify_read_rows_model as model
+    from tests import modify_rows_cases as rc
+
+    def dev(a):
+        signed = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32,
+                  np.dtype(np.uint64): np.int64}
+        return torch.from_numpy(a.view(signed.get(a.dtype, a.dtype))).cuda()
+
+    pairs = [(GenProfile.MIXED, Chain.GenericUlp), (GenProfile.VLAN_V6EH, Chain.VlanUlp),
+             (GenProfile.GENEVE, Chain.GeneveOverV6Tunnel), (GenProfile.MIXED, Chain.UdpParser),
+             (GenProfile.ADVERSARIAL, Chain.GenericUlp)]
+    for k, (prof, chain) in enumerate(pairs):
+        arena, off, lens = ingot_amd.gen_frames(prof, n, seed=seed + 210 + k)
+        recs = ctx.parse(arena, off, lens, chain)
+        if k % 2:
+            ctx.checksum_fill(arena, off, lens, recs)
+        torch.cuda.synchronize()
+        rng = np.random.default_rng(seed + 210 + k)
+        crec = ingot_amd.records_to_numpy(recs)
+        frames = cases.frames_of(arena.cpu().numpy(), off.cpu().numpy().view(np.uint64),
+                                 lens.cpu().numpy())
+        packets = [cases.cut(f, crec[i], rng) for i, f in enumerate(frames)]
+        tables = cases.place(packets, misalign=list(range(16)) + [int(rng.integers(16))],
+                             gap=int(rng.integers(0, 4)))
+        parsed = mrm.parse(tables, chain)
+        pristine, d_tab = dev(tables[0]), [dev(x) for x in tables[1:]]
+        out = torch.zeros((n, 16), dtype=torch.uint8, device="cuda")
+        chunk = torch.zeros(n, dtype=torch.int16, device="cuda")
+        whats = rc2.valid_whats(chain)
+        lists = rc2.random_lists(chain, n, len(whats), seed=seed + k)
+        bytes_bad = recs_bad = chunk_bad = edited = guarded = 0
+        uploads = {}
+        for j, edits in enumerate(lists):
+            what = whats[j]
+            rows = rng.integers(0, rc2.N_ROWS, n).astype(np.uint32)
+            rows[rng.random(n) < 0.2] = ROW_NONE
+            rows[rng.random(n) < 0.05] = rc2.N_ROWS
+            want, w_rec, w_chunk = model.apply(tables, chain, edits, rows, rc2.N_ROWS, what,
+                                               parsed=parsed)
+            d_a = pristine.clone()
+            out.fill_(0xEE)
+            chunk.fill_(-1)
+            ctx.parse_read_modify_rows(d_a, *d_tab, chain, rc.device_edits(torch, edits, uploads),
+                                       rows=dev(rows), n_rows=rc2.N_ROWS, csum=what, out=out,
+                                       chunk=chunk)
+            got = d_a.cpu().numpy()
+            bytes_bad += int((got != want).sum())
+            recs_bad += int((out.cpu().numpy() != w_rec.view(np.uint8).reshape(n, 16))
+                            .any(axis=1).sum())
+            chunk_bad += int((chunk.cpu().numpy().view(np.uint16) != w_chunk).sum())
+            edited += int((want != tables[0]).sum())
+            guarded += int((rows >= rc2.N_ROWS).sum())
+        key = f"modify_read_rows/{prof.name}/{chain.name}"
+        res[key] = {"byte_mismatches": bytes_bad, "record_mismatches": recs_bad,
+                    "chunk_mismatches": chunk_bad, "edit_lists": len(lists), "whats": list(whats),
+                    "bytes_edited": edited, "guarded": guarded,
+                    "ok_packets": int((parsed[0]["status"] == 0).sum()),
+                    "chunks": int(tables[3][-1]), "sums_filled_first": bool(k % 2)}
+        print(key, res[key], flush=True)
+        del arena, off, lens, recs, out, chunk, pristine, d_tab
+        torch.cuda.empty_cache()
+
+
 def emit_read_cases(ctx, n, seed, res):
     """ingot_gpu_emit_packets_read against tests/emit_read_model.py: every
     header stack of tests/emit_csum_cases.py in front of the frames of four
@@ -477,17 +559,19 @@ def main():
                     help="frames per csum case (its reference is a Python model)")
     ap.add_argument("--only", default="",
                     help="'csum' / 'modify_csum' / 'emit_csum' / 'csum_read' / 'modify_read' / "
-                         "'emit_read' / 'emit_rows': run only that case group")
+                         "'emit_read' / 'emit_rows' / 'modify_read_rows': run only that case "
+                         "group")
     args = ap.parse_args()
     if args.only in ("csum", "modify_csum", "emit_csum", "csum_read", "modify_read", "emit_read",
-                     "emit_rows"):
+                     "emit_rows", "modify_read_rows"):
         import ingot_amd
 
         res, t0 = {}, time.time()
         group = {"csum": csum_cases, "modify_csum": modify_csum_cases,
                  "emit_csum": emit_csum_cases, "csum_read": csum_read_cases,
                  "modify_read": modify_read_cases, "emit_read": emit_read_cases,
-                 "emit_rows": emit_rows_cases}[args.only]
+                 "emit_rows": emit_rows_cases,
+                 "modify_read_rows": modify_read_rows_cases}[args.only]
         group(ingot_amd.Context(0), min(args.frames, args.csum_frames), args.seed, res)
         return finish(min(args.frames, args.csum_frames), args.seed, t0, res)
 
