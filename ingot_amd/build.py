@@ -22,7 +22,7 @@ BUILD = PKG / "build"
 LIB = PKG / "lib" / "libingot_gpu.so"
 SOURCES = ["parse.hip", "read.hip", "ring.hip", "flow.hip", "tuple.hip", "header.hip", "packed.hip",
            "pktgen.hip", "pktgen_host.cpp", "stream.hip", "emit.hip", "emit_read.hip", "csum.hip",
-           "flowtable.cpp", "api.cpp", "comm.cpp"]
+           "flowtable.cpp", "resolve.cpp", "api.cpp", "comm.cpp"]
 ARCH = "gfx950"
 
 

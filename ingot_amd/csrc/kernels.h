@@ -1,4 +1,4 @@
-// kernels.h — internal interface between the C ABI (api.cpp) and the HIP
+// kernels.h — internal interface between the C ABI (api.cpp, resolve.cpp) and the HIP
 // kernels: the argument blocks, the tuning record and the launchers of
 // parse.hip, read.hip, ring.hip, tuple.hip, packed.hip, flow.hip, header.hip,
 // emit.hip, emit_read.hip, csum.hip and stream.hip.  Not part of the public ABI.
@@ -68,7 +68,7 @@ struct FlowArgs {
     alignas(16) uint32_t tab16[FLOW_TAB16_DW];  // entry (p, v) at half-word 16p + v
 };
 
-// In-place rewrite (ingot_gpu_parse_modify): api.cpp resolves each ingot_edit's
+// In-place rewrite (ingot_gpu_parse_modify): resolve.cpp resolves each ingot_edit's
 // field to its header kind and BE bit geometry, so the kernel needs no tables.
 enum HdrKind : uint8_t { HK_ETH, HK_VLAN, HK_V4, HK_V6, HK_TCP, HK_UDP, HK_ICMP, HK_GENEVE };
 struct Edit {
@@ -84,7 +84,7 @@ struct ModifyArgs {
 };
 // ingot_gpu_parse_modify_csum: the rewrite's arguments and, after them (so
 // the plain rewrite kernels keep their own argument block, byte for byte),
-// which sums edit k's bytes feed, resolved by api.cpp from the edit's layer
+// which sums edit k's bytes feed, resolved by resolve.cpp from the edit's layer
 // and field, and the sums the call selected.
 struct ModifyCsumArgs {
     ModifyArgs m;
@@ -95,7 +95,7 @@ struct ModifyCsumArgs {
 // (the fixed L4 header), by the L4 sum's IPv4 pseudo-header (the addresses:
 // fed only when the packet's L4 layer has one) or by the tunnel's outer UDP sum.
 enum CsumFeed : uint8_t { FEED_L3 = 1, FEED_L4 = 2, FEED_OUTER = 4, FEED_PSEUDO4 = 8 };
-// ingot_gpu_parse_modify_rows: per-packet operands.  api.cpp resolves each
+// ingot_gpu_parse_modify_rows: per-packet operands.  resolve.cpp resolves each
 // ingot_edit_rows to one piece (a narrow field) or to 4-byte SET pieces (an
 // IPv6 address: 4; a MAC: a 4-byte and a 2-byte one), each an Edit of at most
 // 4 bytes for the shared apply_edit, with where its operand comes from.  A
@@ -176,7 +176,7 @@ struct HeaderArgs {
 };
 hipError_t launch_header(const HeaderArgs& a, hipStream_t s);
 
-// Batched Emit (ingot_gpu_emit_packets / _headers, emit.hip).  api.cpp
+// Batched Emit (ingot_gpu_emit_packets / _headers, emit.hip).  resolve.cpp
 // resolves each ingot_emit_set to the covering bytes of its field in the
 // header block, so the kernel needs no tables.
 struct EmitSet {
@@ -214,7 +214,7 @@ size_t emit_lds_bytes(const EmitArgs& a);
 hipError_t launch_emit(const EmitArgs& a, hipStream_t s);
 
 // Emit with per-packet and per-row operands (ingot_gpu_emit_packets_rows, k_emit's
-// ROWS instantiations in emit.hip).  api.cpp resolves each
+// ROWS instantiations in emit.hip).  resolve.cpp resolves each
 // ingot_emit_set_rows, in list order, to one piece (a narrow field: EmitSet's
 // geometry) or to big-endian pieces of 4 and 2 bytes (an IPv6 address: 4; a
 // MAC: a 4-byte and a 2-byte one), each with where its operand comes from.

@@ -384,23 +384,32 @@ hipError_t launch_parse(const ParseArgs& args, int layout_kind, int chain, int m
 }
 
 // Parse + rewrite: the default windows of the record path.  ARGS = ModifyArgs,
-// or ModifyCsumArgs for the fused checksum update.
+// ModifyCsumArgs for the fused checksum update, or ModifyRowsArgs for
+// per-packet operands, which take k_parse's windows for every layout, slot
+// rings too (k_modify_pipe has no table loads).
+static const ParseArgs& frames_of(const ModifyRowsArgs& a) { return a.p; }  // (no ModifyArgs)
+template <class ARGS>
+static const ParseArgs& frames_of(const ARGS& a) {
+    return edit_args(a).p;
+}
 template <class ARGS>
 static hipError_t launch_modify_as(const ARGS& a, int layout_kind, int chain, const Tuning& t,
                                    hipStream_t s) {
-    const ParseArgs& p = edit_args(a).p;
+    const ParseArgs& p = frames_of(a);
     if (p.n == 0) return hipSuccess;
     const uint32_t g = grid_for(p.n, t.max_blocks);
     const bool tun = chain == INGOT_CHAIN_GENEVE_OVER_V6;
     // Slot rings (slots >= 64 B, no length array): the multi-tile kernel with
     // lane-linear write-back (k_modify_pipe).  Defaults measured on MI355X
     // (DESIGN.md §1c): write-back unit WB, plain staging loads.
-    if (t.pipeline != 1 && !t.window_strided && layout_kind == LAYOUT_STRIDED && !p.len && !tun &&
-        p.stride >= 64u) {
-        if constexpr (std::is_same<ARGS, ModifyCsumArgs>::value)
-            return launch_modify_ring_csum(a, chain, t, s);
-        else
-            return launch_modify_ring(a, chain, t, s);
+    if constexpr (!std::is_same<ARGS, ModifyRowsArgs>::value) {
+        if (t.pipeline != 1 && !t.window_strided && layout_kind == LAYOUT_STRIDED && !p.len &&
+            !tun && p.stride >= 64u) {
+            if constexpr (std::is_same<ARGS, ModifyCsumArgs>::value)
+                return launch_modify_ring_csum(a, chain, t, s);
+            else
+                return launch_modify_ring(a, chain, t, s);
+        }
     }
     if (layout_kind == LAYOUT_STRIDED) {
         if (tun) return launch_chain<8, LAYOUT_STRIDED, OUT_MODIFY>(a, chain, g, s);
@@ -421,20 +430,9 @@ hipError_t launch_modify_csum(const ModifyCsumArgs& a, int layout_kind, int chai
     return launch_modify_as(a, layout_kind, chain, t, s);
 }
 
-// Per-packet operands: launch_modify_as's k_parse windows for every layout;
-// slot rings too (k_modify_pipe has no table loads).
 hipError_t launch_modify_rows(const ModifyRowsArgs& a, int layout_kind, int chain,
                               const Tuning& t, hipStream_t s) {
-    if (a.p.n == 0) return hipSuccess;
-    const uint32_t g = grid_for(a.p.n, t.max_blocks);
-    const bool tun = chain == INGOT_CHAIN_GENEVE_OVER_V6;
-    if (layout_kind == LAYOUT_STRIDED) {
-        if (tun) return launch_chain<8, LAYOUT_STRIDED, OUT_MODIFY>(a, chain, g, s);
-        return a.p.stride <= 64u ? launch_chain<4, LAYOUT_STRIDED, OUT_MODIFY>(a, chain, g, s)
-                                 : launch_chain<3, LAYOUT_STRIDED, OUT_MODIFY>(a, chain, g, s);
-    }
-    return tun ? launch_chain<8, LAYOUT_INDEXED, OUT_MODIFY>(a, chain, g, s)
-               : launch_chain<3, LAYOUT_INDEXED, OUT_MODIFY>(a, chain, g, s);
+    return launch_modify_as(a, layout_kind, chain, t, s);
 }
 
 // Flow mode needs the addresses (IPv6: 32 bytes past byte 22) and ports, so

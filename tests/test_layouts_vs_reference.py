@@ -123,13 +123,13 @@ def test_ipv6_address_offsets_match():
 
 @pytest.mark.skipif(not REF.exists(), reason="reference checkout not present")
 def test_setter_geometry_matches_reference_declaration():
-    """api.cpp's kFieldGeo (the setters' BE geometry, one row per enum
+    """resolve.cpp's kFieldGeo (the setters' BE geometry, one row per enum
     ingot_field) against the same reference declarations."""
     root = LAYOUTS.parent.parent.parent
     header = (root / "include" / "ingot_gpu.h").read_text()
     enum = re.search(r"enum ingot_field \{(.*?)\};", header, re.S).group(1)
     names = [n for n in re.findall(r"INGOT_F_(\w+)", enum) if n != "COUNT"]
-    api = (root / "ingot_amd" / "csrc" / "api.cpp").read_text()
+    api = (root / "ingot_amd" / "csrc" / "resolve.cpp").read_text()
     table = re.search(r"kFieldGeo\[INGOT_F_COUNT\] = \{(.*?)\n\};", api, re.S).group(1)
     rows = re.findall(r"\{ingot_gpu::HK_(\w+), (\d+), (\d+)\}", table)
     assert len(rows) == len(names)

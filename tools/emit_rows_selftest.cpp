@@ -1,6 +1,6 @@
 // emit_rows_selftest.cpp — the argument checks of ingot_gpu_emit_packets_rows
 // as a stand-alone program, for a sanitizer run of that host code
-// (ingot_amd/csrc/api.cpp) without Python or a GPU: every path taken here
+// (ingot_amd/csrc/api.cpp and resolve.cpp) without Python or a GPU: every path taken here
 // returns before any device work.
 //
 //   hipcc -x hip --offload-arch=gfx950 -std=c++17 -O1 -g -Iinclude
@@ -9,7 +9,7 @@
 //       -Wl,-rpath,$PWD/ingot_amd/lib -o tools/bin/emit_rows_selftest
 //   && tools/bin/emit_rows_selftest
 //
-// api.cpp is compiled into the program (so its code carries the checks); the
+// Both sources are compiled into the program (so their code carries the checks); the
 // kernels' launchers come from the library and are never reached.  The set
 // list, the header block and the sums live in heap blocks of exactly their
 // size, so a read past any of them is seen.  Prints "emit_rows selftest: OK".
@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../ingot_amd/csrc/api.cpp"
+#include "../ingot_amd/csrc/resolve.cpp"
 
 #define CHECK(x)                                             \
     do {                                                     \
