@@ -1393,10 +1393,10 @@ int ingot_gpu_parse_modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena,
  *   6. any of d_src, d_off, d_len, d_dst, d_dst_off NULL;
  *   7. then ERANGE from the LDS-fit check.
  *
- * Out of scope: the header-block-only form (ingot_gpu_emit_headers) and the
- * chunked form (ingot_gpu_emit_packets_read) take no tables; wide fields in
- * ingot_emit_set and ingot_edit; a per-packet "emitted" flag (the caller has
- * d_row).
+ * Out of scope: the header-block-only form (ingot_gpu_emit_headers) takes no
+ * tables (the chunked form with tables is ingot_gpu_emit_packets_read_rows);
+ * wide fields in ingot_emit_set and ingot_edit; a per-packet "emitted" flag
+ * (the caller has d_row).
  * ------------------------------------------------------------------------- */
 typedef struct ingot_emit_set_rows {
     uint16_t at;           /* as ingot_emit_set */
@@ -1544,6 +1544,69 @@ int ingot_gpu_parse_read_modify_rows(ingot_gpu_ctx* ctx, uint8_t* d_arena,
                                      const ingot_edit_rows* edits, uint32_t n_edits,
                                      const uint32_t* d_row, uint32_t n_rows,
                                      uint32_t what, ingot_rec* d_out, uint16_t* d_chunk,
+                                     void* stream);
+
+/* ---------------------------------------------------------------------------
+ * Emit over chunked packets with per-packet and per-row header operands:
+ * ingot_gpu_emit_packets_read's chunk lists with ingot_gpu_emit_packets_rows'
+ * setters.  One launch pulls an mblk chain or a header-split packet up,
+ * encapsulates it towards its own flow's endpoint (outer IPv6 destination,
+ * next-hop MAC and VNI from the row the flow resolved to), fills the outer
+ * sums over those bytes, and leaves a packet whose flow has no mapping
+ * un-emitted.  Inbound, with d_from the inner L3 offset of a chunked tunnel
+ * packet and hdr a 14-byte Ethernet header whose MACs are BY_ROW, it cuts the
+ * inner packet out and puts the flow's own Ethernet header in front of it.
+ * No new struct or enum: ingot_emit_set_rows, ingot_emit_sum, ingot_wide_field,
+ * ingot_edit_by and INGOT_ROW_NONE are ingot_gpu_emit_packets_rows'.
+ * Build-defined; tests/emit_read_rows_model.py is the definition.
+ *
+ * Payload, reads, cut.  The tables (d_src, d_seg_off, d_seg_len, d_pkt_seg),
+ * d_from / d_take and their clamps, the cut at 65,535 logical bytes, d_taken,
+ * the 16-B read contract, the never-dereferenced offset of an empty chunk, the
+ * aliasing and overlap rules are exactly ingot_gpu_emit_packets_read's; P_i
+ * and t are its payload and its length.
+ *
+ * Setters, operands, order, sums, row guard.  `sets`, the fields (the wide ones
+ * too), the operand of set k for packet i, `by`, pitch, the list order, the
+ * sums taken after all setters and the bounds of the table reads are exactly
+ * ingot_gpu_emit_packets_rows'.  INGOT_EMIT_LENGTH counts hdr_len + t.
+ *
+ * Equivalence, which is the definition.  For every emitted packet the bytes
+ * are those ingot_gpu_emit_packets_rows writes with the same hdr, sets, sums,
+ * d_row, n_rows and d_dst_off when its source is a linear copy of P_i and
+ * d_len[i] = t.  With no BYTES set, no BY_ROW set and d_row NULL, the
+ * destination and d_taken are byte-identical to ingot_gpu_emit_packets_read
+ * with the same sets and sums.  Every destination byte is stored once, and
+ * nothing outside [d_dst + d_dst_off[i], + hdr_len + t) is stored to.
+ *
+ * Guarded packet (d_row given and d_row[i] >= n_rows).  No byte at or around
+ * d_dst + d_dst_off[i] is stored; no source byte, no table and no entry of
+ * d_seg_off / d_seg_len is read for it (its chunk bounds may be garbage); its
+ * d_pkt_seg, d_from, d_take and d_dst_off entries may be read;
+ * d_taken[i] = 0 when d_taken is given.  With d_row NULL no set may be BY_ROW
+ * (EINVAL) and n_rows is ignored.
+ *
+ * EINVAL, all checked before any device work, in this order:
+ *   1. ctx NULL;
+ *   2. checks 2 to 4 of ingot_gpu_emit_packets_rows (hdr / hdr_len / n_sets /
+ *      NULL sets; per set, in list order; the sums), unchanged;
+ *   3. n == 0 succeeds whatever the device pointers are;
+ *   4. d_dst or d_dst_off NULL;
+ *   5. any of d_src, d_seg_off, d_seg_len, d_pkt_seg NULL;
+ *   6. then ERANGE from the LDS-fit check.
+ *
+ * Out of scope: tables in ingot_gpu_emit_headers; scattering the output into
+ * chunks; the dense (offset << 16) | length table and d_first; TCP / ICMP sum
+ * kinds and inner-frame sums; the C++ mirror (ingot_amd.hpp).
+ * ------------------------------------------------------------------------- */
+int ingot_gpu_emit_packets_read_rows(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
+                                     const ingot_emit_set_rows* sets, uint32_t n_sets,
+                                     const ingot_emit_sum* sums, uint32_t n_sums,
+                                     const uint32_t* d_row, uint32_t n_rows,
+                                     const uint8_t* d_src, const uint64_t* d_seg_off,
+                                     const uint16_t* d_seg_len, const uint32_t* d_pkt_seg,
+                                     const uint16_t* d_from, const uint16_t* d_take, uint64_t n,
+                                     uint8_t* d_dst, const uint64_t* d_dst_off, uint16_t* d_taken,
                                      void* stream);
 
 /*

@@ -717,6 +717,35 @@ class Context:
             _stream(stream, self.device)), "ingot_gpu_emit_packets")
         return dst
 
+    def _emit_set_rows(self, sets, n: int, rows, n_rows: int):
+        """The set list of emit_packets_rows / emit_packets_read_rows, each
+        table validated on the host -> (ingot_emit_set_rows array, tensors kept
+        alive for the call)."""
+        out, keep = [], []
+        for k, e in enumerate(sets):
+            at, field, source, add = e[0], e[1], EmitSource(int(e[2])), e[3]
+            table, by = (e[4] if len(e) > 4 else None), EditBy.PACKET
+            if isinstance(table, tuple):
+                if len(table) != 2 or table[0] != "row":
+                    raise ValueError(f"set {k}: a table operand is a tensor or ('row', tensor)")
+                if rows is None:
+                    raise ValueError(f"set {k}: ('row', tensor) needs `rows`")
+                by, table = EditBy.ROW, table[1]
+            if source in (EmitSource.LENGTH, EmitSource.VALUE):
+                if table is not None:
+                    raise ValueError(f"set {k}: {source.name} takes no table")
+                out.append((at, field, source, add, 0, 0, 0))
+                continue
+            if not hasattr(table, "data_ptr"):
+                raise ValueError(f"set {k}: {source.name} needs a cuda tensor")
+            kind, pitch = self._row_table(f"set {k}'s table", table, field, by == EditBy.ROW, n,
+                                          int(n_rows))
+            if kind != source.name:
+                raise ValueError(f"set {k}: a {kind} table for an EmitSource.{source.name} set")
+            keep.append(table)
+            out.append((at, field, source, add, by, pitch, table.data_ptr()))
+        return emit_set_rows_array(out), keep
+
     def emit_packets_rows(self, hdr: bytes, sets, src, off, lens, dst, dst_off, rows=None,
                           n_rows: int = 0, sums=None, stream=None):
         """emit_packets whose setters take per-packet and per-row operands, the
@@ -744,30 +773,7 @@ class Context:
         if rows is not None and (n_rows < 0 or n_rows > 0xFFFFFFFF):
             raise ValueError("n_rows must fit 32 bits")
         self._on_device(src=src, off=off, lens=lens, dst=dst, dst_off=dst_off, rows=rows)
-        out, keep = [], []
-        for k, e in enumerate(sets):
-            at, field, source, add = e[0], e[1], EmitSource(int(e[2])), e[3]
-            table, by = (e[4] if len(e) > 4 else None), EditBy.PACKET
-            if isinstance(table, tuple):
-                if len(table) != 2 or table[0] != "row":
-                    raise ValueError(f"set {k}: a table operand is a tensor or ('row', tensor)")
-                if rows is None:
-                    raise ValueError(f"set {k}: ('row', tensor) needs `rows`")
-                by, table = EditBy.ROW, table[1]
-            if source in (EmitSource.LENGTH, EmitSource.VALUE):
-                if table is not None:
-                    raise ValueError(f"set {k}: {source.name} takes no table")
-                out.append((at, field, source, add, 0, 0, 0))
-                continue
-            if not hasattr(table, "data_ptr"):
-                raise ValueError(f"set {k}: {source.name} needs a cuda tensor")
-            kind, pitch = self._row_table(f"set {k}'s table", table, field, by == EditBy.ROW, n,
-                                          int(n_rows))
-            if kind != source.name:
-                raise ValueError(f"set {k}: a {kind} table for an EmitSource.{source.name} set")
-            keep.append(table)
-            out.append((at, field, source, add, by, pitch, table.data_ptr()))
-        s = emit_set_rows_array(out)
+        s, keep = self._emit_set_rows(sets, n, rows, int(n_rows))
         cs = emit_sums_array(sums or ())
         h = (ctypes.c_uint8 * max(len(hdr), 1)).from_buffer_copy(hdr or b"\0")
         _lib.check(self._lib.ingot_gpu_emit_packets_rows(
@@ -809,6 +815,43 @@ class Context:
             cs.ctypes.data_as(ctypes.c_void_p), len(cs), _ptr(src), _ptr(seg_off), _ptr(seg_len),
             _ptr(pkt_seg), _ptr(frm), _ptr(take), n, _ptr(dst), _ptr(dst_off), _ptr(taken),
             _stream(stream, self.device)), "ingot_gpu_emit_packets_read")
+        return dst
+
+    def emit_packets_read_rows(self, hdr: bytes, sets, src, seg_off, seg_len, pkt_seg, dst,
+                               dst_off, rows=None, n_rows: int = 0, frm=None, take=None,
+                               taken=None, sums=None, stream=None):
+        """ingot_gpu_emit_packets_read_rows: emit_packets_read's chunk lists,
+        `frm` / `take` / `taken` with emit_packets_rows' `sets` (their table
+        forms, ("row", tensor) included), `rows` / `n_rows` (the row guard) and
+        `sums`.  A packet whose rows[i] >= n_rows is not emitted: no byte of
+        dst is written for it, none of its chunks is read, and taken[i] = 0.
+        Returns dst."""
+        n = pkt_seg.numel() - 1
+        hdr = bytes(hdr)
+        self._arg("src", src, _U8)
+        self._arg("pkt_seg", pkt_seg, _U32, n + 1)
+        self._arg("seg_off", seg_off, _U64)
+        self._arg("seg_len", seg_len, _U16, seg_off.numel())
+        self._arg("dst", dst, _U8)
+        self._arg("dst_off", dst_off, _U64, n)
+        self._arg("frm", frm, _U16, n, optional=True)
+        self._arg("take", take, _U16, n, optional=True)
+        self._arg("taken", taken, _U16, n, optional=True)
+        self._arg("rows", rows, _U32, n, optional=True)
+        if rows is not None and (n_rows < 0 or n_rows > 0xFFFFFFFF):
+            raise ValueError("n_rows must fit 32 bits")
+        self._on_device(src=src, seg_off=seg_off, seg_len=seg_len, pkt_seg=pkt_seg, dst=dst,
+                        dst_off=dst_off, frm=frm, take=take, taken=taken, rows=rows)
+        s, keep = self._emit_set_rows(sets, n, rows, int(n_rows))
+        cs = emit_sums_array(sums or ())
+        h = (ctypes.c_uint8 * max(len(hdr), 1)).from_buffer_copy(hdr or b"\0")
+        _lib.check(self._lib.ingot_gpu_emit_packets_read_rows(
+            self._h, ctypes.addressof(h), len(hdr), s.ctypes.data_as(ctypes.c_void_p), len(s),
+            cs.ctypes.data_as(ctypes.c_void_p), len(cs), _ptr(rows), int(n_rows), _ptr(src),
+            _ptr(seg_off), _ptr(seg_len), _ptr(pkt_seg), _ptr(frm), _ptr(take), n, _ptr(dst),
+            _ptr(dst_off), _ptr(taken), _stream(stream, self.device)),
+            "ingot_gpu_emit_packets_read_rows")
+        del keep
         return dst
 
     def emit_header_blocks(self, hdr: bytes, sets, lens, out, out_off=None, stride: int = 0,

@@ -151,6 +151,12 @@ SIGNATURES = {
         [ctypes.c_void_p, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint32,
          c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u64, c_u8p, c_u8p, c_u8p, ctypes.c_void_p],
     ),
+    "ingot_gpu_emit_packets_read_rows": (
+        ctypes.c_int,
+        [ctypes.c_void_p, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint32,
+         c_u8p, ctypes.c_uint32, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u64, c_u8p, c_u8p,
+         c_u8p, ctypes.c_void_p],
+    ),
     "ingot_gpu_emit_headers": (
         ctypes.c_int,
         [ctypes.c_void_p, c_u8p, ctypes.c_uint32, c_u8p, ctypes.c_uint32, c_u8p, c_u64, c_u8p,

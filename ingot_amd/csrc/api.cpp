@@ -808,6 +808,50 @@ int ingot_gpu_emit_packets_read(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t
     return from_hip(launch_emit_read(a, (hipStream_t)stream));
 }
 
+int ingot_gpu_emit_packets_read_rows(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
+                                     const ingot_emit_set_rows* sets, uint32_t n_sets,
+                                     const ingot_emit_sum* sums, uint32_t n_sums,
+                                     const uint32_t* d_row, uint32_t n_rows,
+                                     const uint8_t* d_src, const uint64_t* d_seg_off,
+                                     const uint16_t* d_seg_len, const uint32_t* d_pkt_seg,
+                                     const uint16_t* d_from, const uint16_t* d_take, uint64_t n,
+                                     uint8_t* d_dst, const uint64_t* d_dst_off, uint16_t* d_taken,
+                                     void* stream) {
+    if (!ctx) return INGOT_GPU_EINVAL;
+    // the header block, pieces and sums as ingot_gpu_emit_packets_rows makes
+    // them, then moved behind the chunk tables' block
+    EmitRowsArgs rows{};
+    if (int e = emit_args(hdr, hdr_len, nullptr, 0, rows.e)) return e;
+    ingot_emit_set narrow[INGOT_MAX_EMIT_SETS];
+    uint32_t n_narrow = 0;
+    if (int e = emit_rows_pieces(sets, n_sets, d_row != nullptr, hdr_len, rows, narrow, n_narrow))
+        return e;
+    if (int e = emit_sums(hdr, hdr_len, narrow, n_narrow, sums, n_sums, rows.e)) return e;
+    if (n == 0) return INGOT_GPU_SUCCESS;
+    if (!d_dst || !d_dst_off) return INGOT_GPU_EINVAL;
+    Frames f;
+    if (int e = chunks_of(d_src, d_seg_off, d_seg_len, d_pkt_seg, n, nullptr, nullptr, f)) return e;
+    EmitReadRowsArgs a{};
+    a.r.e = rows.e;
+    a.n_pieces = rows.n_pieces;
+    std::memcpy(a.p, rows.p, sizeof a.p);
+    if (emit_read_rows_lds_bytes(a) > ctx->lds_bytes) return INGOT_GPU_ERANGE;
+    if (int e = enter(ctx)) return e;
+    a.r.e.src = d_src;
+    a.r.e.dst = d_dst;
+    a.r.e.dst_off = d_dst_off;
+    a.r.e.n = n;
+    a.r.seg_off = f.p.off;
+    a.r.seg_len = f.p.len;
+    a.r.pkt_seg = f.p.pkt_seg;
+    a.r.from = d_from;
+    a.r.take = d_take;
+    a.r.taken = d_taken;
+    a.row = d_row;
+    a.n_rows = n_rows;
+    return from_hip(launch_emit_read_rows(a, (hipStream_t)stream));
+}
+
 int ingot_gpu_emit_headers(ingot_gpu_ctx* ctx, const uint8_t* hdr, uint32_t hdr_len,
                            const ingot_emit_set* sets, uint32_t n_sets, const uint16_t* d_len,
                            uint64_t n, uint8_t* d_out, const uint64_t* d_out_off,

@@ -62,8 +62,6 @@ template <bool COPY> struct Shape {
 #define INGOT_EMIT_UNROLL 4
 #endif
 constexpr uint32_t UNROLL = INGOT_EMIT_UNROLL;  // 64-chunk steps whose loads fly together
-// WaveDesc::mis of a packet the row guard holds back (no packet's dmis | s_mis << 8)
-constexpr uint32_t GUARDED = 0xffffffffu;
 
 // Per-wave LDS: the 64 packets' descriptors, the inclusive prefix of their
 // chunk counts, and each packet's patched header block at its destination's

@@ -158,7 +158,11 @@ __device__ __forceinline__ void build_region(uint8_t* R, uint32_t RS, const u32x
     }
 }
 
-// --- ingot_gpu_emit_packets_rows (k_emit's ROWS instantiations) ------------
+// --- ingot_gpu_emit_packets_rows / _read_rows (the ROWS instantiations) ----
+// What WaveDesc::mis / ReadDesc::dmis holds for a packet the row guard holds
+// back (no packet's misalignment): step 5 returns on it.
+constexpr uint32_t GUARDED = 0xffffffffu;
+
 // The operand of piece e for packet i, whose row index is r.  `total` as in
 // set_value.  A wire-order piece comes back as the big-endian number the setter loop
 // takes: one load and a byte swap from an aligned table, byte loads otherwise.
@@ -182,7 +186,8 @@ __device__ __forceinline__ uint32_t piece_value(const EmitPiece& e, uint64_t i, 
 // The pieces into LDS, for every lane of the prologue waves to read at one
 // address: 32 pieces' fields read from the argument block in two unrolled
 // loops made the compiler keep a private copy of the whole block (scratch).
-__device__ __forceinline__ void load_pieces(EmitPiece* P, const EmitRowsArgs& a, uint32_t block) {
+template <class RowsArgs>  // EmitRowsArgs or EmitReadRowsArgs
+__device__ __forceinline__ void load_pieces(EmitPiece* P, const RowsArgs& a, uint32_t block) {
     const uint32_t* w = reinterpret_cast<const uint32_t*>(a.p);
     for (uint32_t k = threadIdx.x; k < a.n_pieces * (uint32_t)(sizeof(EmitPiece) / 4u); k += block)
         reinterpret_cast<uint32_t*>(P)[k] = w[k];

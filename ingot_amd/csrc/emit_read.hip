@@ -1,5 +1,7 @@
 // emit_read.hip — batched Emit over chunked packets (ingot_gpu_emit_packets_read):
-// pull-up, encapsulation and the outer checksums in one launch.
+// pull-up, encapsulation and the outer checksums in one launch
+// (ingot_gpu_emit_packets_read_rows: the ROWS instantiations, described at
+// k_emit_read).
 //
 // The source of packet i is the chunk list of ingot_gpu_parse_read, cut at
 // 65,535 logical bytes, of which the bytes [f, f + t) are the payload (d_from /
@@ -24,6 +26,8 @@
 // does the same per piece and keeps each piece's bytes under a byte mask.
 // Source reads stay inside the aligned 16-B blocks that hold a byte of a
 // piece; an empty chunk's offset is never turned into an address.
+#include <type_traits>
+
 #include "emit_common.h"
 
 namespace ingot_gpu {
@@ -109,8 +113,24 @@ __device__ __forceinline__ u32x4 piece_block(const Piece& p, uint64_t X) {
     return funnel(lo, hi, sh);
 }
 
-template <bool SUMS>
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_emit_read(EmitReadArgs ar) {
+// The EmitReadArgs of either argument block.
+__device__ __forceinline__ const EmitReadArgs& read_args_of(const EmitReadArgs& a) { return a; }
+__device__ __forceinline__ const EmitReadArgs& read_args_of(const EmitReadRowsArgs& a) { return a.r; }
+
+// ROWS (ingot_gpu_emit_packets_read_rows; its argument block is
+// EmitReadRowsArgs): the prologue also loads the packet's row index, folds the
+// row guard into `live` before the chunk-length walk and takes the setters'
+// operands from the pieces of EmitReadRowsArgs, as k_emit's ROWS instantiations
+// do.  A guarded packet has no chunks to walk, no pieces, no payload and no
+// blocks: the block search never lands on it, d_taken gets 0 and step 5
+// returns on it.  Everything from step 3 on is the same code.
+template <bool SUMS, bool ROWS = false>
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_emit_read(
+    std::conditional_t<ROWS, EmitReadRowsArgs, EmitReadArgs> args) {
+    // by value (the compiler reads every field from the kernel arguments all
+    // the same): bound as a reference it moved blocks of the instantiations
+    // without ROWS out of line, 26 more instructions in each
+    const EmitReadArgs ar = read_args_of(args);
     const EmitArgs& a = ar.e;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     u32x4* tmpl = reinterpret_cast<u32x4*>(smem);
@@ -124,6 +144,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_
     // SUMS: after the regions, the parked blocks, then the accumulators
     u32x4* park = reinterpret_cast<u32x4*>(smem + TB * 16 + sizeof(ReadDesc) + NP * RS);
     uint32_t* acc = reinterpret_cast<uint32_t*>(park + 2u * NP);
+    // ROWS: the pieces, after everything else
+    EmitPiece* pieces = reinterpret_cast<EmitPiece*>(SUMS ? (void*)(acc + NP) : (void*)park);
+    if constexpr (ROWS) load_pieces(pieces, args, BLOCK);
     const bool udp = SUMS && a.sums.udp;
     const uint32_t fpos = (uint32_t)a.sums.udp_at + 6u;  // the UDP checksum field in hdr
     __syncthreads();
@@ -135,16 +158,32 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_
         //    holds logical byte `from` on
         const uint32_t j = wg * WAVE + lane;
         const uint64_t i = base + j;
-        const bool live = i < a.n;
+        const bool in_batch = i < a.n;
+        bool live = in_batch;
+        uint32_t r = 0;  // ROWS: the packet's row index, loaded with its descriptors
+        if constexpr (ROWS) {
+            if (live && args.row) r = gbl(args.row)[i];
+        }
         uint32_t s0 = 0, s1 = 0;
         if (live) {
             s0 = gbl(ar.pkt_seg)[i];
             s1 = gbl(ar.pkt_seg)[i + 1];
             s1 = s1 < s0 ? s0 : s1;  // reversed bounds: no chunks
         }
-        const uint32_t fr = (live && ar.from) ? (uint32_t)gbl(ar.from)[i] : 0u;
+        uint32_t fr = (live && ar.from) ? (uint32_t)gbl(ar.from)[i] : 0u;
         const uint32_t tk = (live && ar.take) ? (uint32_t)gbl(ar.take)[i] : 0xffffu;
-        const uint64_t doff = live ? gbl(a.dst_off)[i] : 0u;
+        uint64_t doff = live ? gbl(a.dst_off)[i] : 0u;
+        if constexpr (ROWS) {
+            // the row guard, before the walk: no chunk bounds, so no entry of
+            // seg_len / seg_off is read; the descriptors loaded above are
+            // dropped unused
+            if (args.row && r >= args.n_rows) {
+                live = false;
+                s0 = s1 = 0u;
+                fr = 0u;
+                doff = 0u;
+            }
+        }
 #pragma unroll
         for (uint32_t k = 0; k <= PIECES; ++k) wd.start[k][j] = 0xffffffffu;
         uint32_t g = 0, cnt = 0, cur = s1, tabled_end = 0;
@@ -163,11 +202,14 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_
         const uint32_t f = min(fr, g);
         const uint32_t L = min(tk, g - f);  // t: the payload bytes of this packet
         wd.start[PIECES][j] = cnt == PIECES ? min(tabled_end, L) : L;
-        if (live && ar.taken) ar.taken[i] = (uint16_t)L;
+        // a guarded packet's walk was empty: L = 0 is what its d_taken gets
+        if (in_batch && ar.taken) ar.taken[i] = (uint16_t)L;
         uint32_t v[INGOT_MAX_EMIT_SETS];
+        if constexpr (!ROWS) {
 #pragma unroll
-        for (uint32_t s = 0; s < INGOT_MAX_EMIT_SETS; ++s)
-            v[s] = (s < a.n_sets && live) ? set_value(a.sets[s], i, H + L) : 0u;
+            for (uint32_t s = 0; s < INGOT_MAX_EMIT_SETS; ++s)
+                v[s] = (s < a.n_sets && live) ? set_value(a.sets[s], i, H + L) : 0u;
+        }
         uint8_t* D = a.dst + doff;
         const uint32_t T = H + L;
         const uint32_t dmis = (uint32_t)((uintptr_t)D & 15u);
@@ -180,7 +222,9 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_
         //    sums then measured 0.3 % slower
         //    (profiles/r18_csum_emit_shared_ab.json).  (2b) its sums' start
         uint8_t* R = regions + j * RS;
-        if (H && live) {
+        if constexpr (ROWS) {
+            build_region_rows(R, RS, tmpl, pieces, args.n_pieces, H, i, r, live, dmis, T);
+        } else if (H && live) {
             for (uint32_t m = 0; m < RS / 16u; ++m) {
                 const uint32_t tb = 16u + 16u * m - dmis;
                 reinterpret_cast<u32x4*>(R)[m] = funnel(tmpl[tb >> 4], tmpl[(tb >> 4) + 1], tb & 15u);
@@ -205,7 +249,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_
         wd.dst[j] = (uint64_t)(uintptr_t)D;
         wd.pfx[j] = P;
         wd.len[j] = L;
-        wd.dmis[j] = dmis;
+        wd.dmis[j] = (ROWS && !live) ? GUARDED : dmis;
         wd.cur[j] = cur;
         wd.s1[j] = s1;
         const uint32_t wtotal = (uint32_t)__shfl((int)P, (int)WAVE - 1);
@@ -225,6 +269,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_
 
     // 4. the wave's blocks, 64 per step and UNROLL steps at a time: block k
     //    belongs to the first packet whose inclusive prefix exceeds k
+    // ROWS keeps the UNROLL steps: 63 / 57 VGPRs as they are without it
     constexpr uint32_t U = UNROLL;
     for (uint32_t k0 = wg * WAVE * U; k0 < total; k0 += W * WAVE * U) {
         uint32_t q[U], c[U];
@@ -334,6 +379,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_num_sgpr(96))) void k_
         __syncthreads();
         const uint32_t slot = threadIdx.x / NP, j = threadIdx.x % NP;
         if (slot >= 2u || base + j >= a.n) return;
+        if (ROWS && wd.dmis[j] == GUARDED) return;  // nothing parked, nothing to store
         finish_parked(a, fpos, slot, wd.dmis[j], H + wd.len[j], (uint8_t*)(uintptr_t)wd.dst[j],
                       park + slot * NP + j, acc + j);
     }
@@ -347,6 +393,8 @@ constexpr size_t emit_read_smem(uint32_t H) {
 }
 // gfx950: 160 KiB of LDS per workgroup.
 static_assert(emit_read_smem<true>(INGOT_MAX_EMIT_HDR) <= 160u * 1024u, "k_emit_read LDS > 160 KiB");
+static_assert(emit_read_smem<true>(INGOT_MAX_EMIT_HDR) + sizeof(EmitReadRowsArgs::p) <= 160u * 1024u,
+              "k_emit_read<sums, rows> LDS > 160 KiB");
 static_assert(BLOCK >= 2 * NP, "sums: one lane per parked block");
 
 template <bool SUMS>
@@ -368,6 +416,21 @@ size_t emit_read_lds_bytes(const EmitReadArgs& a) {
 hipError_t launch_emit_read(const EmitReadArgs& a, hipStream_t s) {
     if (a.e.n == 0) return hipSuccess;
     return (a.e.sums.v4 || a.e.sums.udp) ? go<true>(a, s) : go<false>(a, s);
+}
+
+// The rows kernels: k_emit_read's launch shape and LDS (sums or not), and the pieces.
+size_t emit_read_rows_lds_bytes(const EmitReadRowsArgs& a) { return emit_read_lds_bytes(a.r) + sizeof(a.p); }
+
+hipError_t launch_emit_read_rows(const EmitReadRowsArgs& a, hipStream_t s) {
+    if (a.r.e.n == 0) return hipSuccess;
+    const uint64_t blocks = (a.r.e.n + NP - 1) / NP;
+    if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
+    const size_t smem = emit_read_rows_lds_bytes(a);
+    if (a.r.e.sums.v4 || a.r.e.sums.udp)
+        hipLaunchKernelGGL((k_emit_read<true, true>), dim3((uint32_t)blocks), dim3(BLOCK), smem, s, a);
+    else
+        hipLaunchKernelGGL((k_emit_read<false, true>), dim3((uint32_t)blocks), dim3(BLOCK), smem, s, a);
+    return hipGetLastError();
 }
 
 }  // namespace ingot_gpu

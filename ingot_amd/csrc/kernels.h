@@ -270,6 +270,22 @@ static_assert(sizeof(EmitReadArgs) <= 4096, "EmitReadArgs exceeds the 4 KiB kern
 size_t emit_read_lds_bytes(const EmitReadArgs& a);
 hipError_t launch_emit_read(const EmitReadArgs& a, hipStream_t s);
 
+// The two together (ingot_gpu_emit_packets_read_rows, k_emit_read's ROWS
+// instantiations): EmitReadArgs with no sets of its own in r.e, then what
+// EmitRowsArgs has behind its `e`.  A block of its own again, so the
+// EmitReadArgs kernels keep theirs.
+struct EmitReadRowsArgs {
+    EmitReadArgs r;
+    const uint32_t* row;  // optional: per-packet row index (the row guard)
+    uint32_t n_rows;
+    uint32_t n_pieces;
+    EmitPiece p[EMIT_MAX_PIECES];
+};
+static_assert(sizeof(EmitReadRowsArgs) <= 4096,
+              "EmitReadRowsArgs exceeds the 4 KiB kernel-argument limit");
+size_t emit_read_rows_lds_bytes(const EmitReadRowsArgs& a);
+hipError_t launch_emit_read_rows(const EmitReadRowsArgs& a, hipStream_t s);
+
 // Batched Internet checksums (ingot_gpu_checksum_verify / _fill, csum.hip).
 struct CsumArgs {
     uint8_t* arena;        // written only when `fill`

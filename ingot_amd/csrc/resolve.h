@@ -1,7 +1,8 @@
 // resolve.h — the public edit, set and sum lists (include/ingot_gpu.h) resolved
 // to the kernels' argument blocks (kernels.h).  Pure host functions: no HIP
 // runtime call, and the context only for its NULL test, so they run without a
-// device (tools/api_args_selftest.cpp, tools/emit_rows_selftest.cpp).  The C
+// device (tools/api_args_selftest.cpp, tools/emit_rows_selftest.cpp,
+// tools/emit_read_rows_selftest.cpp).  The C
 // ABI's entry points (api.cpp) add the frames or chunk tables and launch.
 #pragma once
 

@@ -247,6 +247,17 @@ hipError_t launch_emit_read(const EmitReadArgs& a, hipStream_t s) {
         A(a.seg_len), A(a.pkt_seg), A(a.from), A(a.take), A(a.taken));
     return done();
 }
+// ingot_gpu_emit_packets_read_rows: linked, and in no group of the corpus
+// (tools/emit_read_rows_selftest.cpp has its argument checks)
+size_t emit_read_rows_lds_bytes(const EmitReadRowsArgs& a) {
+    put("emit_read_rows_lds_bytes ");
+    return 8192u + a.r.e.hdr_len + 32u * a.n_pieces;
+}
+hipError_t launch_emit_read_rows(const EmitReadRowsArgs& a, hipStream_t s) {
+    put("launch_emit_read_rows(s=%llx ", A(s));
+    put_emit(a.r.e);
+    return done();
+}
 hipError_t launch_csum(const CsumArgs& a, hipStream_t s) {
     put("launch_csum(s=%llx arena=%llx off=%llx len=%llx stride=%llu what=%llu n=%llu rec=%llx "
         "out=%llx fill=%llu ",

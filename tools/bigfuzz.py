@@ -25,11 +25,15 @@ tests/emit_rows_cases.py, rows from the flow bins, whole arenas against
 tests/emit_rows_model.py, same cap), and the rewrite over chunked packets with
 per-packet operands (`modify_read_rows`, only with --only: modify_read's five
 sets with random mixed lists, tables, guards and every `what`, against
-tests/modify_read_rows_model.py, same cap).
+tests/modify_read_rows_model.py, same cap), and the emit over chunked packets
+with per-row operands (`emit_read_rows`, only with --only: emit_rows' stacks,
+table forms and rows over emit_read's cut frames with random from / take, the
+guarded packets' chunk descriptors unusable, whole arenas and d_taken against
+tests/emit_read_rows_model.py, same cap).
 
     python tools/bigfuzz.py [--frames 4000000] [--seed 1234]
                             [--only csum|modify_csum|emit_csum|csum_read|modify_read|emit_read|
-                                    emit_rows|modify_read_rows]
+                                    emit_rows|modify_read_rows|emit_read_rows]
 """
 from __future__ import annotations
 
@@ -542,6 +546,82 @@ def emit_rows_cases(ctx, n, seed, res):
         torch.cuda.empty_cache()
 
 
+def emit_read_rows_cases(ctx, n, seed, res):
+    """ingot_gpu_emit_packets_read_rows against tests/emit_read_rows_model.py:
+    emit_rows_cases' stacks, table forms and rows (the flow bin; 1 packet in
+    16 a row past the table) over emit_read_cases' cut frames and random
+    d_from / d_take.  A packet that is not emitted has chunk offsets of 2^60,
+    chunk lengths of 65,535 and a destination outside the arena; the whole
+    destination arena and d_taken are compared."""
+    import torch
+
+    import ingot_amd
+    from ingot_amd import Chain, GenProfile
+    from tests import csum_read_cases as chunks
+    from tests import emit_read_model
+    from tests import emit_read_rows_cases as rrc
+    from tests import emit_read_rows_model as model
+    from tests import emit_rows_cases as rc
+
+    def dev(a):
+        a = np.ascontiguousarray(a)
+        signed = {np.dtype(np.uint16): np.int16, np.dtype(np.uint32): np.int32,
+                  np.dtype(np.uint64): np.int64}
+        return torch.from_numpy(a.view(signed.get(a.dtype, a.dtype))).cuda()
+
+    rng = np.random.default_rng(seed)
+    bins = 4096
+    for k, prof in enumerate((GenProfile.MIXED, GenProfile.ADVERSARIAL)):
+        arena, off, lens = ingot_amd.gen_frames(prof, n, seed=seed + 190 + k)
+        flow = ctx.flow_hist(arena, off, lens, Chain.GenericUlp, bins=bins)
+        rows = flow.cpu().numpy().view(np.uint32).copy()
+        rows[rng.random(n) < 1 / 16] = bins
+        live = rows < bins
+        crec = ingot_amd.records_to_numpy(ctx.parse(arena, off, lens, Chain.GenericUlp))
+        ln = lens.cpu().numpy()
+        frames = chunks.frames_of(arena.cpu().numpy(), off.cpu().numpy().view(np.uint64), ln)
+        packets = [chunks.cut(f, crec[i], rng) for i, f in enumerate(frames)]
+        src, seg_off, seg_len, pkt_seg = chunks.place(
+            packets, misalign=list(range(16)) + [int(rng.integers(16))], gap=int(rng.integers(0, 4)))
+        whole = rng.random(n) < 0.5
+        frm = np.where(whole, 0, rng.integers(0, ln.astype(np.int64) + 10)).astype(np.uint16)
+        take = np.where(rng.random(n) < 0.5, 65535,
+                        rng.integers(0, ln.astype(np.int64) + 10)).astype(np.uint16)
+        t = emit_read_model.linearise(src, seg_off, seg_len, pkt_seg, frm, take)[2]
+        seg_off, seg_len = seg_off.copy(), seg_len.copy()
+        for i in np.nonzero(~live)[0]:
+            seg_off[int(pkt_seg[i]):int(pkt_seg[i + 1])] = rrc.POISON_OFF
+            seg_len[int(pkt_seg[i]):int(pkt_seg[i + 1])] = 65535
+        tables = (src, seg_off, seg_len, pkt_seg)
+        d_tab, d_rows = [dev(x) for x in tables], dev(rows)
+        del arena, off, lens
+        for name in rc.STACKS:
+            for form in rc.FORMS:
+                case = rc.stack(name, form, n, bins, rng)
+                dst_off, size = rrc.pack_live(len(case.hdr) + t.astype(np.int64), live, rng)
+                dst_off[~live] = rrc.POISON_DST
+                want, taken_want = model.apply(np.full(size, 0xA5, np.uint8), case.hdr,
+                                               case.host_sets(), case.sums, *tables, dst_off,
+                                               rows, bins, frm, take)
+                dst = dev(np.full(size, 0xA5, np.uint8))
+                taken = dev(np.full(n, 0xA5A5, np.uint16))
+                backing = {key: dev(v) for key, v in case.backing.items()}
+                ctx.emit_packets_read_rows(case.hdr, case.device_sets(backing), *d_tab, dst,
+                                           dev(dst_off), rows=d_rows, n_rows=bins, frm=dev(frm),
+                                           take=dev(take), taken=taken, sums=case.sums)
+                torch.cuda.synchronize()
+                key = f"emit_read_rows/{prof.name}/{name}/{form}"
+                res[key] = {"byte_mismatches": int((dst.cpu().numpy() != want).sum()),
+                            "taken_mismatches": int((taken.cpu().numpy().view(np.uint16)
+                                                     != taken_want).sum()),
+                            "arena_bytes": size, "chunks": int(pkt_seg[-1]),
+                            "emitted": int(live.sum()), "not_emitted": int((~live).sum())}
+                print(key, res[key], flush=True)
+                del dst, taken, backing
+        del d_tab
+        torch.cuda.empty_cache()
+
+
 def finish(n, seed, t0, res):
     out = {"frames_per_case": n, "seed": seed, "wall_s": round(time.time() - t0, 1),
            "cases": res,
@@ -559,11 +639,11 @@ def main():
                     help="frames per csum case (its reference is a Python model)")
     ap.add_argument("--only", default="",
                     help="'csum' / 'modify_csum' / 'emit_csum' / 'csum_read' / 'modify_read' / "
-                         "'emit_read' / 'emit_rows' / 'modify_read_rows': run only that case "
-                         "group")
+                         "'emit_read' / 'emit_rows' / 'modify_read_rows' / 'emit_read_rows': run "
+                         "only that case group")
     args = ap.parse_args()
     if args.only in ("csum", "modify_csum", "emit_csum", "csum_read", "modify_read", "emit_read",
-                     "emit_rows", "modify_read_rows"):
+                     "emit_rows", "modify_read_rows", "emit_read_rows"):
         import ingot_amd
 
         res, t0 = {}, time.time()
@@ -571,7 +651,8 @@ def main():
                  "emit_csum": emit_csum_cases, "csum_read": csum_read_cases,
                  "modify_read": modify_read_cases, "emit_read": emit_read_cases,
                  "emit_rows": emit_rows_cases,
-                 "modify_read_rows": modify_read_rows_cases}[args.only]
+                 "modify_read_rows": modify_read_rows_cases,
+                 "emit_read_rows": emit_read_rows_cases}[args.only]
         group(ingot_amd.Context(0), min(args.frames, args.csum_frames), args.seed, res)
         return finish(min(args.frames, args.csum_frames), args.seed, t0, res)
 

@@ -58,12 +58,33 @@ every packet taken from a table, rows
 
 checks once that a and b, and c, d and e, leave identical bytes.
 
+`--read-rows` measures ingot_gpu_emit_packets_read_rows instead (DESIGN.md
+4.18): `--read`'s two-chunk tables and `--rows`' endpoint table, rows
+
+  a  read_csum          ingot_gpu_emit_packets_read with the UDP sum;
+  b  rr_no_table        the new call with the same narrow sets and no table
+                        (the same walk: what the new prologue costs by itself);
+  c  rr_by_packet       b + the IPv6 destination and Ethernet destination
+                        BY_PACKET (n-row tables);
+  d  rr_by_row          the same BY_ROW from a 65,536-row table indexed by the
+                        flow bins (uncounted packets take row 0);
+  dg rr_by_row_guard    d with the bins as they are: uncounted packets are not
+                        emitted and their chunks not walked;
+  e  read_modify_rows   today's route to d's bytes: emit_packets_read with the
+                        UDP sum, then ingot_gpu_parse_modify_rows over the
+                        output (GENEVE_OVER_V6, the two wide fields BY_ROW,
+                        OUTER_L4), which parses by itself;
+
+checks once that a and b, and d and e (and c), leave identical bytes and
+d_taken, and says whether b's median lies inside a's min-max of rounds and d
+below e's fastest round.
+
 `--usage-only` compiles ingot_amd/csrc/emit.hip, emit_read.hip and csum.hip with
 -Rpass-analysis=kernel-resource-usage and writes the kernels' figures (no GPU
 needed); `--usage FILE` attaches such a file to the result.
 
     python tools/emit_csum_probe.py [--frames N] [--reps 5] [--rounds 5] [--read]
-        [--rows] [--against head] [--usage FILE] [--out profiles/r12_emit_csum_probe.json]
+        [--rows] [--read-rows] [--against head] [--usage FILE] [--out profiles/r12_emit_csum_probe.json]
 """
 from __future__ import annotations
 
@@ -92,8 +113,11 @@ def resource_usage() -> dict:
     names = {"k_emitILb1ELb1ELb1EE": "k_emit<copy, sums, rows>",
              "k_emitILb1ELb0ELb1EE": "k_emit<copy, rows>",
              "k_emitILb1ELb1ELb0EE": "k_emit<copy, sums>", "k_emitILb1ELb0ELb0EE": "k_emit<copy>",
-             "k_emitILb0ELb0ELb0EE": "k_emit<headers>", "k_emit_readILb1EE": "k_emit_read<sums>",
-             "k_emit_readILb0EE": "k_emit_read", "6k_csumE": "k_csum", "11k_csum_readE": "k_csum_read"}
+             "k_emitILb0ELb0ELb0EE": "k_emit<headers>",
+             "k_emit_readILb1ELb1EE": "k_emit_read<sums, rows>",
+             "k_emit_readILb0ELb1EE": "k_emit_read<rows>",
+             "k_emit_readILb1ELb0EE": "k_emit_read<sums>", "k_emit_readILb0ELb0EE": "k_emit_read",
+             "6k_csumE": "k_csum", "11k_csum_readE": "k_csum_read"}
     for line in err.splitlines():
         m = re.search(r"remark: +([A-Za-z ]+?)(?: \[[^\]]*\])?: (\S+)", line)
         if not m:
@@ -408,6 +432,106 @@ def child_rows(args) -> dict:
             "d_max_le_e_min": bool(runs["d_rows_by_row"]["max"] <= runs["e_emit_modify_rows"]["min"])}
 
 
+def child_read_rows(args) -> dict:
+    import torch
+
+    from ingot_amd import CSUM_OUTER_L4, Chain, EditOp, EmitSource, WideField
+
+    d = setup(args.frames, args.copies)
+    ctx, n, H = d["ctx"], args.frames, d["H"]
+    arena, off, lens, hdr, dst_off = d["arena"], d["off"], d["lens"], d["hdr"], d["dst_off"]
+    sets, sums, bins = d["sets"], d["sums"], 1 << 16
+    # --read's tables: the frames cut in place at payload_off
+    rc = ctx.parse(arena, off, lens, Chain.GenericUlp)
+    L = lens.to(torch.int32) & 0xFFFF
+    pay = rc[:, 12].to(torch.int32) | (rc[:, 13].to(torch.int32) << 8)
+    pay = torch.where(rc[:, 0] == 0, torch.minimum(pay, L), L)
+    so = torch.stack((off, off + pay.to(torch.int64)), dim=1).reshape(-1).contiguous()
+    sl = torch.stack((pay.to(torch.int16), (L - pay).to(torch.int16)), dim=1).reshape(-1).contiguous()
+    ps = (torch.arange(n + 1, dtype=torch.int32, device="cuda") * 2).contiguous()
+    del rc
+    # --rows' table: one (bins, 32) table, underlay IPv6 at 0, next-hop MAC at 16
+    g = torch.Generator(device="cuda").manual_seed(2)
+    table = torch.randint(0, 256, (bins, 32), dtype=torch.uint8, device="cuda", generator=g)
+    v6_row, mac_row = table[:, 0:16], table[:, 16:22]
+    flow = ctx.flow_hist(arena, off, lens, Chain.GenericUlp, bins=bins)
+    counted = flow >= 0
+    rows_all = torch.where(counted, flow, torch.zeros_like(flow)).contiguous()
+    v6_pkt = v6_row[rows_all.to(torch.int64)].contiguous()
+    mac_pkt = mac_row[rows_all.to(torch.int64)].contiguous()
+    V6D, MACD, B = WideField.V6_DESTINATION, WideField.ETH_DESTINATION, EmitSource.BYTES
+    by_packet = sets + [(14, V6D, B, 0, v6_pkt), (0, MACD, B, 0, mac_pkt)]
+    by_row = sets + [(14, V6D, B, 0, ("row", v6_row)), (0, MACD, B, 0, ("row", mac_row))]
+    edits = [(1, V6D, EditOp.SET, ("row", v6_row)), (0, MACD, EditOp.SET, ("row", mac_row))]
+    TUN = Chain.GeneveOverV6Tunnel
+    taken = torch.empty(n, dtype=torch.int16, device="cuda")
+
+    def pick(dst):
+        return d["pick"]() if dst is None else dst
+
+    def read_csum(dst=None, tk=None):
+        ctx.emit_packets_read(hdr, sets, arena, so, sl, ps, pick(dst), dst_off, taken=tk,
+                              sums=sums)
+
+    def rr(the_sets, dst, tk, **kw):
+        ctx.emit_packets_read_rows(hdr, the_sets, arena, so, sl, ps, pick(dst), dst_off,
+                                   taken=tk, sums=sums, **kw)
+
+    def rr_no_table(dst=None, tk=None):
+        rr(sets, dst, tk)
+
+    def rr_by_packet(dst=None, tk=None):
+        rr(by_packet, dst, tk)
+
+    def rr_by_row(dst=None, tk=None):
+        rr(by_row, dst, tk, rows=rows_all, n_rows=bins)
+
+    def rr_by_row_guard(dst=None, tk=None):
+        rr(by_row, dst, tk, rows=flow, n_rows=bins)
+
+    def read_modify_rows(dst=None, tk=None):
+        dst = pick(dst)
+        ctx.emit_packets_read(hdr, sets, arena, so, sl, ps, dst, dst_off, taken=tk, sums=sums)
+        ctx.parse_modify_rows(dst, dst_off, d["tl"], TUN, edits, rows=rows_all, n_rows=bins,
+                              csum=CSUM_OUTER_L4)
+
+    x, y = d["dsts"][0], d["dsts"][1 % len(d["dsts"])]
+    tx = torch.empty_like(taken)
+    same = {}
+    for name, old, new in (("a_equals_b", read_csum, rr_no_table),
+                           ("c_equals_d", rr_by_packet, rr_by_row),
+                           ("e_equals_d", read_modify_rows, rr_by_row)):
+        for t in (x, y):
+            t.fill_(0xA5)
+        tx.fill_(0x5A5A)
+        taken.fill_(0x5A5A)
+        old(x, tx)
+        new(y, taken)
+        torch.cuda.synchronize()
+        same[name] = bool(torch.equal(x, y) and torch.equal(tx, taken)) if x is not y else None
+        if same[name] is False:
+            same[name + "_bytes_differ"] = int((x != y).sum().item())
+    runs = timed({"a_read_csum": read_csum, "b_rr_no_table": rr_no_table,
+                  "c_rr_by_packet": rr_by_packet, "d_rr_by_row": rr_by_row,
+                  "dg_rr_by_row_guard": rr_by_row_guard, "e_read_modify_rows": read_modify_rows},
+                 args.reps, args.rounds)
+    for r in runs.values():
+        r["min"], r["max"] = min(r["rounds"]), max(r["rounds"])
+    us = {k: r["us"] for k, r in runs.items()}
+    a = runs["a_read_csum"]
+    return {"frames": n, "hdr_len": H, "payload_bytes": d["payload"], "emitted_bytes": d["total"],
+            "chunks": 2 * n, "table_rows": bins, "table_pitch": 32,
+            "counted_packets": int(counted.sum().item()),
+            "copies": args.copies, "reps": args.reps, "same_bytes": same, "runs": runs,
+            "rounds_spread_max": max(r["spread"] for r in runs.values()),
+            "b_over_a": round(us["b_rr_no_table"] / us["a_read_csum"], 4),
+            "b_median_inside_a_rounds": bool(a["min"] <= us["b_rr_no_table"] <= a["max"]),
+            "c_over_b": round(us["c_rr_by_packet"] / us["b_rr_no_table"], 4),
+            "d_over_c": round(us["d_rr_by_row"] / us["c_rr_by_packet"], 4),
+            "d_over_e": round(us["d_rr_by_row"] / us["e_read_modify_rows"], 4),
+            "d_below_e_min": bool(us["d_rr_by_row"] < runs["e_read_modify_rows"]["min"])}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=1 << 23)
@@ -422,6 +546,8 @@ def main():
     ap.add_argument("--child", default=None)
     ap.add_argument("--read", action="store_true", help="the chunked emit's rows (DESIGN 4.12)")
     ap.add_argument("--rows", action="store_true", help="emit_packets_rows' rows (DESIGN 4.15)")
+    ap.add_argument("--read-rows", action="store_true",
+                    help="emit_packets_read_rows' rows (DESIGN 4.18)")
     args = ap.parse_args()
     if args.usage_only:
         out = resource_usage()
@@ -429,6 +555,7 @@ def main():
         print(json.dumps(child_main(args) if args.child == "main"
                          else child_read(args) if args.child == "read"
                          else child_rows(args) if args.child == "rows"
+                         else child_read_rows(args) if args.child == "read_rows"
                          else child_plain(args.child, args)), flush=True)
         return
     else:
@@ -442,7 +569,8 @@ def main():
                 sys.exit(p.returncode or 1)
             return json.loads(p.stdout.strip().splitlines()[-1])
 
-        out = {"what": __doc__.split("\n\n")[0], **run("read" if args.read else "rows" if args.rows else "main")}
+        out = {"what": __doc__.split("\n\n")[0], **run("read_rows" if args.read_rows else "read" if args.read else "rows" if args.rows
+                     else "main")}
         print(json.dumps(out), flush=True)
         if args.against:
             rows = []
